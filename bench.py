@@ -8,6 +8,19 @@ generated on the GPU (include/mtcp_gpu_pktgen.h) and stay in HBM; results
 (40 B per packet) are written to HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5|f1|f3|f4] [--strong]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and no more: it generates the
+batch, warms up, times the K steps and prints the line (metric, value, unit,
+ms_per_step, the roofline of the timed launches).  --full adds every other
+leg to the same line, each as before and each with its own on/off option:
+the measured read ceiling, the CPU baseline, the PCIe-inclusive rate, the
+4 096-frame aggregate, C4's per-GPU step at N = 1, and on the f rows their
+access-pattern ceiling, fused and end-to-end figures and CPU baselines.
+--dump-outputs DIR writes the result records of the last timed step, one
+DIR/<field>.npy per record field (dump_outputs below); the frames depend only
+on the config and its seed, so two builds run with the same arguments can be
+compared record for record.
 
 Without --config the workload is BASELINE.json's config for that N: C2
 (1 M x 1500 B) on one GPU, C4 (2 M x 1500 B per GPU, 16 M at N = 8) on
@@ -137,6 +150,15 @@ def parse():
                     help="default: c2 at --gpus 1, c4 (2 M x 1500 B per GPU) at --gpus N > 1")
     ap.add_argument("--strong", action="store_true",
                     help="split the config's whole batch N ways (C4: 16 M) instead of N x its per-GPU batch")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure (read ceiling, CPU baseline, "
+                         "PCIe-inclusive rate, small batch, C4's per-GPU step; on the f rows their "
+                         "ceiling, fused / end-to-end figures and CPU baseline); the options below "
+                         "that switch single legs on or off apply to a --full run only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the result records of the last step as "
+                         "DIR/<field>.npy (float32 / float64, a fixed seeded sample of the packets "
+                         "when the whole batch would pass the size budget)")
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "on", "off"])
     ap.add_argument("--cpu-sample", type=int, default=1 << 20,
                     help="packets in the CPU sample (default: the whole 1-GPU batch, "
@@ -599,6 +621,38 @@ def c4_per_gpu(ctx, dev, stream, steps, warmup):
                     "/ N / this value is the scaling of identical per-GPU work"}
 
 
+DUMP_BUDGET = 56_000_000   # bytes of .npy data per run, all ranks together
+DUMP_SEED = 0x6d746370     # the sample of packets a large batch is dumped at
+
+
+def dump_outputs(path, records, rank=0, world=1):
+    """--dump-outputs: the result records of the last timed step, as the
+    caller of mtcp_gpu_rx_chunk_dev receives them, one PATH/<field>.npy per
+    record field (include/mtcp_gpu.h) — float64 for the 32-bit fields, float32
+    for the narrower ones, both exact — and PATH/packet_index.npy, the index
+    in this rank's batch of the packet each row belongs to.  Every packet
+    when that fits this rank's share of DUMP_BUDGET, else a fixed sample
+    (seeded, ascending) so that two builds dump the same packets.  At N > 1
+    each rank writes its own files, rank<r>_<field>.npy.  Returns the number
+    of packets written."""
+    names = records.dtype.names
+    per_packet = 8 + sum(8 if records.dtype[f].itemsize > 2 else 4 for f in names)
+    n = len(records)
+    keep = min(n, DUMP_BUDGET // world // per_packet)
+    if keep == n:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    np.save(os.path.join(path, prefix + "packet_index.npy"), idx.astype(np.float64))
+    rows = records[idx]
+    for f in names:
+        kind = np.float64 if records.dtype[f].itemsize > 2 else np.float32
+        np.save(os.path.join(path, f"{prefix}{f}.npy"), rows[f].astype(kind))
+    return keep
+
+
 def _cpu_time(fn, reps=3):
     best = None
     for _ in range(reps):
@@ -614,12 +668,14 @@ def run_row(args):
     from mtcp_amd import gpu
     if int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.gpus != 1:
         raise SystemExit("the f-row benches run on one GPU")
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the rx records: configs c1..c5")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     host_cpus = bind_to_device(0, args.numa)
     stream = torch.cuda.Stream(dev)
     torch.cuda.set_stream(stream)
-    want_cpu = args.cpu_baseline in ("on", "auto")
+    want_cpu = args.full and args.cpu_baseline in ("on", "auto")
     line = {"metric": f"{args.config}: " + ROWS[args.config], "n_gpus": 1, "steps": args.steps,
             "warmup": args.warmup, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "data": "synthetic", "config": {"workload": args.config},
@@ -636,9 +692,9 @@ def run_row(args):
         # idempotent after the first fill: every step rewrites the same checks
         step = lambda: ctx.tx_fill_dev(d_buf, d_desc, n, 6, stream=stream)
         # the access pattern's own ceiling on these frames, measured now,
-        # before the fill's launches (as read_ceiling is for rx)
+        # before the fill's launches (as read_ceiling is for rx); --full only
         try:
-            ceil = patch_ceiling(d_buf, d_desc, n, stream)
+            ceil = patch_ceiling(d_buf, d_desc, n, stream) if args.full else None
         except Exception as exc:      # never costs the line
             ceil = repr(exc)
         wall, kern = _timed(step, args.steps, args.warmup, stream)
@@ -700,16 +756,18 @@ def run_row(args):
                                     "record's lines) + 4 B bin written per packet"}
         # HashFlow fused into the rx pass (mtcp_gpu_rx_chunk_flow_dev): the
         # bin leaves with the record, so the record is never read back
-        rx_step = lambda: ctx.rx_chunk_dev(d_buf, d_desc, n, 6, d_out, stream=stream)
-        fused_step = lambda: ctx.rx_chunk_flow_dev(d_buf, d_desc, n, 6, d_out, bins, stream=stream)
-        _, k_rx = _timed(rx_step, args.steps, args.warmup, stream)
-        _, k_fused = _timed(fused_step, args.steps, args.warmup, stream)
-        line["fused_rx_flow"] = {"rx_us": round(k_rx * 1e6, 2), "rx_flow_fused_us": round(k_fused * 1e6, 2),
-                                 "rx_then_flow_us": round((k_rx + kern) * 1e6, 2),
-                                 "saved_us": round((k_rx + kern - k_fused) * 1e6, 2),
-                                 "note": "HIP events per launch, C2 batch (1 M x 1500 B): rx alone, "
-                                         "rx with the bin fused, rx followed by the separate "
-                                         "flow_hash kernel"}
+        # (--full: two more timed runs)
+        if args.full:
+            rx_step = lambda: ctx.rx_chunk_dev(d_buf, d_desc, n, 6, d_out, stream=stream)
+            fused_step = lambda: ctx.rx_chunk_flow_dev(d_buf, d_desc, n, 6, d_out, bins, stream=stream)
+            _, k_rx = _timed(rx_step, args.steps, args.warmup, stream)
+            _, k_fused = _timed(fused_step, args.steps, args.warmup, stream)
+            line["fused_rx_flow"] = {"rx_us": round(k_rx * 1e6, 2), "rx_flow_fused_us": round(k_fused * 1e6, 2),
+                                     "rx_then_flow_us": round((k_rx + kern) * 1e6, 2),
+                                     "saved_us": round((k_rx + kern - k_fused) * 1e6, 2),
+                                     "note": "HIP events per launch, C2 batch (1 M x 1500 B): rx alone, "
+                                             "rx with the bin fused, rx followed by the separate "
+                                             "flow_hash kernel"}
         if want_cpu:
             import oracle
             res = d_out.cpu().numpy().view(gpu.RESULT_DTYPE)
@@ -764,11 +822,12 @@ def run_row(args):
         b_n = struct.unpack("<I", socket.inet_aton("10.0.0.1"))[0]
         d_n = struct.unpack("<I", socket.inet_aton("192.168.0.1"))[0]
         p_n = struct.unpack("<H", struct.pack(">H", 80))[0]
-        t_gpu = _cpu_time(lambda: ctx.addr_pool_search(3, nq, b_n, num_addr, d_n, p_n, True))
-        line["search_end_to_end"] = {"value": round(total / t_gpu / 1e9, 3), "unit": "Gcandidates/s",
-                                     "note": "mtcp_gpu_addr_pool_search host call: queue map, "
-                                             "count / scan / emit compaction, D2H of one core's "
-                                             "entries; wall clock, best of 3"}
+        if args.full:
+            t_gpu = _cpu_time(lambda: ctx.addr_pool_search(3, nq, b_n, num_addr, d_n, p_n, True))
+            line["search_end_to_end"] = {"value": round(total / t_gpu / 1e9, 3), "unit": "Gcandidates/s",
+                                         "note": "mtcp_gpu_addr_pool_search host call: queue map, "
+                                                 "count / scan / emit compaction, D2H of one core's "
+                                                 "entries; wall clock, best of 3"}
         if want_cpu:
             import oracle
             t = _cpu_time(lambda: oracle.addr_pool_search(None, 3, nq, b_n, num_addr, d_n, p_n, 1))
@@ -895,7 +954,7 @@ def main():
             step()
         torch.cuda.synchronize()
     ceiling = my_ceiling_us = None
-    if args.ceiling == "on":
+    if args.full and args.ceiling == "on":
         # The box's read ceiling on this rank's own frame buffer, measured
         # right before the kernel so that both see the same device state
         # (a cold device runs its first launches a few us slow: C2 at
@@ -996,6 +1055,8 @@ def main():
         d_out.cpu().numpy().tofile(os.path.join(args.dump_records, f"records_rank{rank}.bin"))
         json.dump({"rank": rank, "world": world, "first_index": sh.first_index, "count": sh.count},
                   open(os.path.join(args.dump_records, f"shard_rank{rank}.json"), "w"))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out.cpu().numpy().view(ctx.result_dtype), rank, world)
 
     if world > 1:
         tb = torch.tensor([frame_bytes, sh.count, payload], dtype=torch.int64)
@@ -1011,8 +1072,9 @@ def main():
     extra = {}
     # the CPU baseline at every N: rank 0 alone at N = 1 (1 core and its
     # share), every rank at once on its own cores at N > 1 (a collective step)
-    want_cpu = args.cpu_baseline in ("on", "auto")
-    want_pcie = args.pcie in ("on", "auto")     # every rank: a collective step when N > 1
+    # (every leg from here to ctx.close(): --full only)
+    want_cpu = args.full and args.cpu_baseline in ("on", "auto")
+    want_pcie = args.full and args.pcie in ("on", "auto")     # every rank: a collective step when N > 1
     if want_cpu:
         host, hdesc = host_prefix(d_buf, sh.desc, max_pkts=args.cpu_sample)
         if world == 1:
@@ -1027,12 +1089,12 @@ def main():
         del host
     want_c4 = args.c4_per_gpu == "on" or (args.c4_per_gpu == "auto" and world == 1 and args.config == "c2"
                                           and not args.per_gpu and not compact)
-    if world == 1 and want_c4:
+    if args.full and world == 1 and want_c4:
         try:
             extra["c4_per_gpu"] = c4_per_gpu(ctx, dev, stream, args.steps, args.warmup)
         except Exception as exc:      # never costs the headline line
             extra["c4_per_gpu"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and args.small_batch != "off":
+    if args.full and rank == 0 and world == 1 and args.small_batch != "off":
         try:
             extra["small_batch"] = small_batch(ctx, dev, stream)
         except Exception as exc:      # never costs the headline line

@@ -5,6 +5,7 @@ benches refuse multi-GPU runs rather than reporting a partial number."""
 import json
 import os
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -153,6 +154,58 @@ def test_read_ceiling_probe_is_built_and_exported(bench, monkeypatch):
     monkeypatch.setattr("sys.argv", ["bench.py"])
     a = bench.parse()
     assert (a.ceiling, a.numa) == ("on", "on")
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(bench, monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs) == (True, "d")
+
+
+def _records(n):
+    from mtcp_amd import RESULT_DTYPE
+    rng = np.random.default_rng(5)
+    r = np.zeros(n, RESULT_DTYPE)
+    for f in RESULT_DTYPE.names:
+        r[f] = rng.integers(0, 1 << (8 * RESULT_DTYPE[f].itemsize), n, dtype=np.uint64)
+    return r
+
+
+def test_dump_outputs_small_batch_is_whole_and_exact(bench, tmp_path):
+    """Every field of every record, exactly (float32 holds 16 bits, float64
+    32), with the packet indices beside them."""
+    r = _records(1000)
+    r["seq"][:2] = (0xFFFFFFFF, 0x01000001)      # not representable in float32
+    assert bench.dump_outputs(str(tmp_path), r) == 1000
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{f}.npy" for f in (*r.dtype.names, "packet_index"))
+    assert np.array_equal(np.load(tmp_path / "packet_index.npy"), np.arange(1000))
+    for f in r.dtype.names:
+        got = np.load(tmp_path / f"{f}.npy")
+        assert got.dtype == (np.float64 if r.dtype[f].itemsize > 2 else np.float32)
+        assert np.array_equal(got.astype(np.uint64), r[f].astype(np.uint64)), f
+
+
+def test_dump_outputs_large_batch_is_a_fixed_sample_within_budget(bench, tmp_path, monkeypatch):
+    """Past the budget: the same ascending sample of packets on every call,
+    and the files together stay under the budget (64 MB at most for a run)."""
+    assert bench.DUMP_BUDGET <= 64_000_000
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1 << 20)
+    r = _records(50000)
+    a, b = tmp_path / "a", tmp_path / "b"
+    keep = bench.dump_outputs(str(a), r)
+    assert 0 < keep < 50000 and bench.dump_outputs(str(b), r) == keep
+    idx = np.load(a / "packet_index.npy").astype(np.int64)
+    assert len(idx) == keep and np.all(np.diff(idx) > 0) and idx[-1] < 50000
+    assert np.array_equal(idx, np.load(b / "packet_index.npy").astype(np.int64))
+    assert np.array_equal(np.load(a / "rss_hash.npy"), r["rss_hash"][idx].astype(np.float64))
+    data = sum(np.load(a / f).nbytes for f in os.listdir(a))
+    assert data == keep * (data // keep) <= 1 << 20 < (keep + 1) * (data // keep)
+    # two ranks: each its own files and half the budget
+    half = bench.dump_outputs(str(a), r, rank=1, world=2)
+    assert half == (1 << 19) // (data // keep) and len(np.load(a / "rank1_verdict.npy")) == half
 
 
 def _rank(r, pci, kern, node=0):

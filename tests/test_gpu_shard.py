@@ -74,7 +74,7 @@ def _bench_ranks(tmp_path, config, per_gpu, world=2, launcher="torchrun"):
     env.update(MTCP_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1")
     args = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--config", config,
             "--per-gpu", str(per_gpu), "--steps", "3", "--warmup", "1", "--cpu-baseline", "off",
-            "--pcie", "off", "--dump-records", str(dump)]
+            "--pcie", "off", "--dump-records", str(dump), "--full"]
     if launcher == "torchrun":
         port = 29600 + os.getpid() % 300
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
@@ -134,7 +134,7 @@ def test_bench_default_n2_runs_c4_with_cpu_baseline(gpu, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MTCP_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--per-gpu", str(1 << 17),
-           "--steps", "3", "--warmup", "1", "--cpu-sample", str(1 << 14), "--pcie", "off"]
+           "--steps", "3", "--warmup", "1", "--cpu-sample", str(1 << 14), "--pcie", "off", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -165,11 +165,11 @@ def _clean_env(**kw):
 
 
 def test_bench_default_n1_carries_c4_per_gpu(gpu):
-    """the N = 1 default line (C2) also times C4's
+    """the N = 1 default line (C2) of a --full run also times C4's
     per-GPU step — rank 0's 2 M x 1500 B shard, two launches — in the same
     run, so the driver's 1 -> 8 ratio can be read on identical per-GPU work."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-           "--cpu-baseline", "off", "--pcie", "off", "--small-batch", "off", "--ceiling", "off"]
+           "--cpu-baseline", "off", "--pcie", "off", "--small-batch", "off", "--ceiling", "off", "--full"]
     line = _bench_line(cmd, _clean_env())
     assert line["n_gpus"] == 1 and line["config"]["workload"].startswith("c2: 1 M x 1500 B")
     c4 = line["c4_per_gpu"]
@@ -187,7 +187,7 @@ def test_bench_driver_form_eight_ranks_on_one_device(gpu):
     share at once, the PCIe-inclusive leg of all 8 ranks, the run's wall time
     and host memory.  (The timings mean nothing: 8 ranks share one GPU.)"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--per-gpu", str(1 << 14),
-           "--steps", "3", "--warmup", "1", "--cpu-sample", str(1 << 13)]
+           "--steps", "3", "--warmup", "1", "--cpu-sample", str(1 << 13), "--full"]
     line = _bench_line(cmd, _clean_env(MTCP_BENCH_DEVICE="0"))
     assert line["n_gpus"] == 8 and line["config"]["workload"].startswith("c4: 128 K x 1500 B")
     assert line["config"]["packets_total"] == 8 << 14 and line["scaling"] == "weak"
@@ -205,3 +205,36 @@ def test_bench_driver_form_eight_ranks_on_one_device(gpu):
     assert len({r["gpu_pci"] for r in ro["per_rank"]}) == 1 == ro["distinct_gpus"]
     assert ro["kern_ms_spread"] >= 1.0
     assert line["config"]["note"].startswith("MTCP_BENCH_DEVICE=0") and "warning" not in line["config"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_records(gpu, tmp_path):
+    """A run without --full carries the headline and its roofline and none of
+    the legs beside it; --steps is the number of timed steps; --dump-outputs
+    writes every field of the last step's records, equal to one launch over
+    the same batch made here."""
+    n, seed = 1 << 14, 3
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c3", "--per-gpu", str(n),
+           "--steps", "3", "--warmup", "1", "--prewarm-s", "0", "--dump-outputs", str(dump)]
+    line = _bench_line(cmd, _clean_env(), timeout=120)
+    assert (line["n_gpus"], line["steps"], line["warmup"]) == (1, 3, 1)
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "GB/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["roofline"]["avg_launch_ms"] > 0
+    for leg in ("cpu_baseline", "pcie_inclusive", "small_batch", "c4_per_gpu"):
+        assert leg not in line
+    assert "read_ceiling" not in line["roofline"]
+    desc, nbytes = pktgen.layout(n, "bimodal", 6, seed)
+    b = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    d = to_dev(desc)
+    gpu.pktgen_dev(b, d, n, 6, seed)
+    out = dev_results(n)
+    with gpu.Context(0, rss=True, rss_queues=8, rss_endian=True) as ctx:
+        ctx.rx_chunk_dev(b, d, n, 6, out)
+        torch.cuda.synchronize()
+    want = out.cpu().numpy().view(RESULT_DTYPE)
+    assert sorted(os.listdir(dump)) == sorted(f"{f}.npy" for f in (*RESULT_DTYPE.names, "packet_index"))
+    assert np.array_equal(np.load(dump / "packet_index.npy"), np.arange(n))
+    for f in RESULT_DTYPE.names:
+        got = np.load(dump / f"{f}.npy")
+        assert got.dtype == (np.float64 if RESULT_DTYPE[f].itemsize > 2 else np.float32)
+        assert np.array_equal(got, want[f].astype(got.dtype)), f

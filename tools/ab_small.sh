@@ -7,7 +7,7 @@ a=$1; b=$2; n=$3; shift 3
 for i in $(seq 1 $n); do
   for cfg in "$@"; do
     for d in $a $b; do
-      (cd $d && timeout -k 10 120 python bench.py --config $cfg --cpu-baseline off --pcie off) | grep '^{' | python3 -c "
+      (cd $d && timeout -k 10 120 python bench.py --full --config $cfg --cpu-baseline off --pcie off) | grep '^{' | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); sb=d.get('small_batch',{})
 print(json.dumps({'tree':'$d','config':'$cfg','round':$i,'kernel_us':round(d['roofline']['avg_launch_ms']*1e3,2),'frac':d['roofline']['frac'],'small_batch_us':sb.get('us_per_launch')}))" || exit 1
     done

@@ -10,4 +10,4 @@ bash tools/gpu_steps.sh \
 # the self-launched multi-rank path, rehearsed with every rank on device 0
 # (the driver's 2/4/8-GPU runs use one device per rank)
 bash tools/gpu_steps.sh \
-  "fc_n4|200|MTCP_BENCH_DEVICE=0 python bench.py --gpus 4 --per-gpu 262144 --pcie off --small-batch off"
+  "fc_n4|200|MTCP_BENCH_DEVICE=0 python bench.py --full --gpus 4 --per-gpu 262144 --pcie off --small-batch off"

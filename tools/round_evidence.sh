@@ -21,19 +21,19 @@ bash tools/gpu_steps.sh \
   "p1|200|bash tools/profile_config.sh c1 gpurun_out/prof_c1" \
   "pf3|200|bash tools/profile_config.sh f3 gpurun_out/prof_f3" \
   "tr|60|python3 tools/update_profiles.py --traffic c1 c2 c3 c3_compact c5 f1 f3" \
-  "bc1|150|python bench.py --config c1" \
-  "bc2|150|python bench.py --config c2" \
-  "bc3|150|python bench.py --config c3" \
-  "bc3_compact|150|python bench.py --config c3 --record compact" \
-  "bc4|150|python bench.py --config c4" \
-  "bc5|200|python bench.py --config c5" \
-  "bf1|150|python bench.py --config f1" \
-  "bf3|150|python bench.py --config f3" \
-  "bf4|150|python bench.py --config f4"
+  "bc1|150|python bench.py --full --config c1" \
+  "bc2|150|python bench.py --full --config c2" \
+  "bc3|150|python bench.py --full --config c3" \
+  "bc3_compact|150|python bench.py --full --config c3 --record compact" \
+  "bc4|150|python bench.py --full --config c4" \
+  "bc5|200|python bench.py --full --config c5" \
+  "bf1|150|python bench.py --full --config f1" \
+  "bf3|150|python bench.py --full --config f3" \
+  "bf4|150|python bench.py --full --config f4"
 else
 bash tools/gpu_steps.sh \
   "c2x5|300|for i in 1 2 3 4 5; do python3 bench.py --gpus 1 --steps 20 --warmup 5 || exit 1; done" \
-  "bn8|300|MTCP_BENCH_DEVICE=0 python3 bench.py --gpus 8 --per-gpu 131072 --steps 20 --warmup 5" \
+  "bn8|300|MTCP_BENCH_DEVICE=0 python3 bench.py --full --gpus 8 --per-gpu 131072 --steps 20 --warmup 5" \
   "iso|60|python -u -m tests.hwq_isolation" \
   "txhang|120|MTCP_GPU_TX=1 MTCP_GPU_PIPELINE=1 MTCP_GPU_TX_STALL_AFTER=2 MTCP_GPU_STALL_US=1500000 MTCP_GPU_WAIT_TIMEOUT_MS=100 oracle/_ref/dropin_tx /tmp/txhang.bin 4096 observe" \
   "txsw|120|MTCP_GPU_TX=0 oracle/_ref/dropin_tx /tmp/txsw.bin 4096 observe && MTCP_GPU_TX=1 oracle/_ref/dropin_tx /tmp/txgpu.bin 4096 observe && cmp /tmp/txhang.bin /tmp/txsw.bin && cmp /tmp/txgpu.bin /tmp/txsw.bin && echo tx-frames-identical" \
