@@ -44,6 +44,10 @@
  *   mtcp_gpu_addr_pool_search / _rss_queue_map_dev
  *       the RSS-friendly address search of CreateAddressPoolPerCore
  *       (mtcp/src/addr_pool.c:155-178) over GetRSSCPUCore (mtcp/src/rss.c:90-103).
+ *   mtcp_gpu_rx_tcpopt_chunk_dev / _rx_tcpopt_ptrs_dev / _rx_chunk_opts (mtcp_gpu_tcpopt.h)
+ *       the option walks behind the flow lookup: ParseTCPTimestamp
+ *       (mtcp/src/tcp_util.c:61-92, called at tcp_in.c:109) and ParseTCPOptions
+ *       (tcp_util.c:14-59, called at tcp_in.c:72 and :88), one record per packet.
  *   mtcp_gpu_dev_ioctl
  *       io_module_func.dev_ioctl (mtcp/src/include/io_module.h:67) for the
  *       checksum commands PKT_RX_IP_CSUM / PKT_RX_TCP_CSUM / PKT_TX_IP_CSUM /
@@ -252,8 +256,9 @@ void mtcp_gpu_close(mtcp_gpu_ctx *ctx);
  * Bound every wait of the context's synchronous calls to timeout_us
  * (0: no bound, the default).  Each call computes one deadline when it
  * starts and polls the GPU until then instead of blocking; the calls are
- * mtcp_gpu_rx_chunk, _rx_ptrs, _tx_fill, _tx_fill_ptrs (whose
- * _tx_fill_ptrs_for argument, when non-zero, overrides the limit),
+ * mtcp_gpu_rx_chunk, _rx_chunk_opts (mtcp_gpu_tcpopt.h), _rx_ptrs, _tx_fill,
+ * _tx_fill_ptrs (whose _tx_fill_ptrs_for argument, when non-zero, overrides
+ * the limit),
  * _flow_hash, _addr_pool_search, _reserve, _sync and _close, and the calls
  * of the context's rxqs (mtcp_gpu_rxq.h: create, flush, wait, destroy; an
  * rxq takes the limit its context has when it is created).

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmtcp_gpu.so")
 
-# Every symbol include/mtcp_gpu.h and include/mtcp_gpu_pktgen.h declare.
+# Every symbol the headers under include/ declare.
 EXPORTS = (
     "mtcp_gpu_abi_version", "mtcp_gpu_strerror", "mtcp_gpu_device_count", "mtcp_gpu_device_pci_bus_id",
     "mtcp_gpu_open",
@@ -25,6 +25,7 @@ EXPORTS = (
     "mtcp_gpu_flow_hash_dev", "mtcp_gpu_flow_hash", "mtcp_gpu_rss_queue_map_dev",
     "mtcp_gpu_addr_pool_search", "mtcp_gpu_pktgen_dev",
     "mtcp_gpu_rxq_create", "mtcp_gpu_rxq_destroy", "mtcp_gpu_rxq_push", "mtcp_gpu_rxq_push_chunk",
+    "mtcp_gpu_rx_tcpopt_chunk_dev", "mtcp_gpu_rx_tcpopt_ptrs_dev", "mtcp_gpu_rx_chunk_opts",
     "mtcp_gpu_rxq_pending", "mtcp_gpu_rxq_flush", "mtcp_gpu_rxq_flush_async", "mtcp_gpu_rxq_wait", "mtcp_gpu_rxq_wait_for", "mtcp_gpu_rxq_get", "mtcp_gpu_rxq_get16", "mtcp_gpu_rxq_frame", "mtcp_gpu_rxq_reset",
 )
 
@@ -84,6 +85,9 @@ def lib() -> ctypes.CDLL:
                                        i32),
         "mtcp_gpu_addr_pool_search": ([vp, i32, i32, u32, i32, u32, ctypes.c_uint16, i32, vp, u32,
                                        ctypes.POINTER(u32)], i32),
+        "mtcp_gpu_rx_tcpopt_chunk_dev": ([vp, vp, u64, vp, u32, u32, vp, vp, vp], i32),
+        "mtcp_gpu_rx_tcpopt_ptrs_dev": ([vp, vp, u16p, u32, vp, vp, vp], i32),
+        "mtcp_gpu_rx_chunk_opts": ([vp, vp, u64, vp, u32, u32, vp, vp], i32),
         "mtcp_gpu_pktgen_dev": ([vp, u64, vp, u32, u32, u64, u64, vp], i32),
         "mtcp_gpu_rxq_create": ([ctypes.POINTER(vp), vp, u32, u64], i32),
         "mtcp_gpu_rxq_destroy": ([vp], None),

@@ -39,6 +39,15 @@ RX_ERROR_VERDICTS = (3, 4, 8, 9)   # ProcessPacket ret < 0 (eth_in.c:49-53)
 ADDR_ENTRY_DTYPE = np.dtype([("saddr", "<u4"), ("sport", "<u2"), ("rsvd", "<u2")])
 assert ADDR_ENTRY_DTYPE.itemsize == 8
 
+# struct mtcp_gpu_tcpopt (include/mtcp_gpu_tcpopt.h): ParseTCPTimestamp's and
+# ParseTCPOptions' outputs per packet (mtcp/src/tcp_util.c:14-92)
+TCPOPT_DTYPE = np.dtype([("ts_val", "<u4"), ("ts_ref", "<u4"), ("ts_recent", "<u4"), ("mss", "<u2"),
+                         ("wscale", "u1"), ("flags", "u1")])
+assert TCPOPT_DTYPE.itemsize == 16
+# its flags
+TCPOPT_TS_FOUND, TCPOPT_MSS, TCPOPT_WSCALE, TCPOPT_SACK_PERMIT = 0x01, 0x02, 0x04, 0x08
+TCPOPT_SAW_TIMESTAMP, TCPOPT_TS_UNPINNED, TCPOPT_SYN_UNPINNED = 0x20, 0x40, 0x80
+
 NUM_BINS_FLOWS = 131072      # mtcp/src/include/fhash.h:7
 FLOW_NONE = 0xFFFFFFFF
 MIN_PORT, MAX_PORT = 1025, 65536   # mtcp/src/include/addr_pool.h:7-8

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/mtcp_gpu.h"
+#include "../../include/mtcp_gpu_tcpopt.h"
 #include "ctx_internal.hpp"
 #include "dispatch.hpp"
 #include "flow_kernels.hpp"
@@ -24,6 +25,7 @@
 #include "park.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
+#include "tcpopt_kernels.hpp"
 #include "wait.hpp"
 
 namespace {
@@ -52,6 +54,12 @@ struct Stage {
     uint8_t *h_out = nullptr;                   // D2H -> caller data
     uint64_t h_out_cap = 0;
     uint32_t pend_first = 0, pend_cnt = 0;      // records of this stage's batch not yet copied out
+    // mtcp_gpu_rx_chunk_opts only: the batch's option records (kStagePkts of
+    // them, allocated by the first such call), their bounce buffer, and where
+    // a bounded call's pending ones go (set with pend_cnt; null: none)
+    mtcp_gpu_tcpopt *d_opt = nullptr;
+    mtcp_gpu_tcpopt *h_opt = nullptr;
+    mtcp_gpu_tcpopt *pend_opt = nullptr;
 };
 
 using mtcp_wait::Deadline;
@@ -320,6 +328,12 @@ void stage_release_pkts(Stage &s, bool may_free) {
     s.d_out = nullptr;
     s.pkt_cap = 0;
 }
+constexpr size_t kStageOptBytes = (size_t)kStagePkts * sizeof(mtcp_gpu_tcpopt);
+void stage_release_opts(Stage &s, bool may_free) {
+    mtcp_park::release(s.d_opt, kStageOptBytes, mtcp_park::kDevice, may_free);
+    mtcp_park::release(s.h_opt, kStageOptBytes, mtcp_park::kHost, may_free);
+    s.d_opt = s.h_opt = nullptr;
+}
 void stage_release_host(Stage &s, bool may_free) {
     mtcp_park::release(s.h_in, s.h_in_cap, mtcp_park::kHost, may_free);
     mtcp_park::release(s.h_out, s.h_out_cap, mtcp_park::kHost, may_free);
@@ -433,8 +447,10 @@ int finish_call(mtcp_gpu_ctx *ctx, int rc, const Deadline &dl, int nstages, uint
     }
     for (int i = 0; i < nstages; ++i) {
         Stage &s = ctx->stage[i];
-        if (rc == MTCP_GPU_OK && s.pend_cnt && out_b)
+        if (rc == MTCP_GPU_OK && s.pend_cnt && out_b) {
             memcpy(out_b + (size_t)s.pend_first * rec, s.h_out, (size_t)s.pend_cnt * rec);
+            if (s.pend_opt) memcpy(s.pend_opt, s.h_opt, (size_t)s.pend_cnt * sizeof(mtcp_gpu_tcpopt));
+        }
         s.pend_cnt = 0;
     }
     return rc;
@@ -447,8 +463,46 @@ int stage_collect(mtcp_gpu_ctx *ctx, Stage &s, uint8_t *out_b, size_t rec, const
     const int rc = waited(ctx, drain(s.stream, dl));
     if (rc != MTCP_GPU_OK) return rc;
     memcpy(out_b + (size_t)s.pend_first * rec, s.h_out, (size_t)s.pend_cnt * rec);
+    if (s.pend_opt) memcpy(s.pend_opt, s.h_opt, (size_t)s.pend_cnt * sizeof(mtcp_gpu_tcpopt));
     s.pend_cnt = 0;
     return MTCP_GPU_OK;
+}
+
+// The option records' staging of a stage (mtcp_gpu_rx_chunk_opts): allocated
+// once, at full stage size, so it never grows under a batch in flight.
+int stage_opts(Stage &s, bool bounce) {
+    if (!s.d_opt && !HIP_OK(mtcp_park::alloc(&s.d_opt, kStageOptBytes, mtcp_park::kDevice)))
+        return MTCP_GPU_ENOMEM;
+    if (bounce && !s.h_opt && !HIP_OK(mtcp_park::alloc(&s.h_opt, kStageOptBytes, mtcp_park::kHost)))
+        return MTCP_GPU_ENOMEM;
+    return MTCP_GPU_OK;
+}
+
+// The option kernel (tcpopt_kernels.hpp) over the frames of kp, reading the
+// rx records at `res` (this context's record form); one lane per packet, up
+// to 8 workgroups per CU, grid-stride beyond.
+template <bool PTRS>
+int launch_tcpopt(mtcp_gpu_ctx *ctx, const mg::KParams &kp, const void *res, mtcp_gpu_tcpopt *opt,
+                  hipStream_t st) {
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (kp.n == 0) return MTCP_GPU_OK;
+    mg::OptParams op{};
+    op.buf = kp.buf;
+    op.buf_len = kp.buf_len;
+    op.base_sub = kp.base_sub;
+    op.desc = kp.desc;
+    op.ptrs = kp.ptrs;
+    op.lens = kp.lens;
+    op.n = kp.n;
+    op.off_shift = kp.off_shift;
+    op.res = res;
+    op.opt = reinterpret_cast<uint4 *>(opt);
+    const dim3 grid(std::min<uint32_t>((kp.n + mg::kBlock - 1) / mg::kBlock, (uint32_t)ctx->num_cu * 8));
+    if (kp.compact)
+        hipLaunchKernelGGL((mg::tcpopt_kernel<PTRS, true>), grid, dim3(mg::kBlock), 0, st, op);
+    else
+        hipLaunchKernelGGL((mg::tcpopt_kernel<PTRS, false>), grid, dim3(mg::kBlock), 0, st, op);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
 // The Toeplitz tables of one RSS key on one device (build_rss_tables):
@@ -630,6 +684,7 @@ void mtcp_gpu_close(mtcp_gpu_ctx *ctx) {
         stage_release_buf(s, may_free);
         stage_release_pkts(s, may_free);
         stage_release_host(s, may_free);
+        stage_release_opts(s, may_free);
     }
     mtcp_park::release(ctx->h_gather, ctx->h_gather_cap, mtcp_park::kHost, may_free);
     mtcp_park::release(ctx->h_gather_desc, (size_t)ctx->h_gather_desc_cap * sizeof(mtcp_gpu_desc),
@@ -814,8 +869,22 @@ namespace {
 // pinned bounce buffers (`owned`: buf / desc already are the context's own
 // pinned gather and are not copied again), so that no copy the call gives up
 // on at its deadline can touch the caller's memory afterwards.
+// mtcp_gpu_rx_chunk_opts: the option kernel behind a stage's rx launch, on the
+// stage's stream, over the same frames and the records rx just wrote, and the
+// batch's option records on their way out (dst: the caller's, for this batch).
+int opts_batch(mtcp_gpu_ctx *ctx, Stage &s, const mg::KParams &kp, mtcp_gpu_tcpopt *dst, bool bounce) {
+    int rc = stage_opts(s, bounce);
+    if (rc == MTCP_GPU_OK) rc = launch_tcpopt<false>(ctx, kp, s.d_out, s.d_opt, s.stream);
+    if (rc == MTCP_GPU_OK &&
+        !HIP_OK(hipMemcpyAsync(bounce ? s.h_opt : dst, s.d_opt, (size_t)kp.n * sizeof(mtcp_gpu_tcpopt),
+                               hipMemcpyDeviceToHost, s.stream)))
+        rc = MTCP_GPU_EIO;
+    return rc;
+}
+
 int rx_host(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len, const mtcp_gpu_desc *desc, uint32_t n,
-            uint32_t off_shift, mtcp_gpu_result *out, bool owned, const Deadline &dl) {
+            uint32_t off_shift, mtcp_gpu_result *out, bool owned, const Deadline &dl,
+            mtcp_gpu_tcpopt *opts = nullptr) {
     int rc = MTCP_GPU_OK;
     uint8_t *const out_b = reinterpret_cast<uint8_t *>(out);
     const size_t rec = (size_t)record_size(ctx);
@@ -856,11 +925,13 @@ int rx_host(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len, const mtcp_
                                        hipMemcpyHostToDevice, s.stream)))
                 rc = MTCP_GPU_EIO;
             if (rc == MTCP_GPU_OK) rc = launch<mg::kRxChunk>(ctx, kp, s.stream, &hint);
+            if (rc == MTCP_GPU_OK && opts) rc = opts_batch(ctx, s, kp, opts + first, bounce);
             if (rc == MTCP_GPU_OK &&
                 !HIP_OK(hipMemcpyAsync(bounce ? s.h_out : out_b + first * rec, s.d_out, cnt * rec,
                                        hipMemcpyDeviceToHost, s.stream)))
                 rc = MTCP_GPU_EIO;
-            if (rc == MTCP_GPU_OK && bounce) s.pend_first = first, s.pend_cnt = cnt;
+            if (rc == MTCP_GPU_OK && bounce)
+                s.pend_first = first, s.pend_cnt = cnt, s.pend_opt = opts ? opts + first : nullptr;
         }
     } else {
         uint32_t first = 0;
@@ -909,11 +980,13 @@ int rx_host(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len, const mtcp_
                                        hipMemcpyHostToDevice, s.stream)))
                 rc = MTCP_GPU_EIO;
             if (rc == MTCP_GPU_OK) rc = launch<mg::kRxChunk>(ctx, kp, s.stream, &hint);
+            if (rc == MTCP_GPU_OK && opts) rc = opts_batch(ctx, s, kp, opts + first, bounce);
             if (rc == MTCP_GPU_OK &&
                 !HIP_OK(hipMemcpyAsync(bounce ? s.h_out : out_b + first * rec, s.d_out, cnt * rec,
                                        hipMemcpyDeviceToHost, s.stream)))
                 rc = MTCP_GPU_EIO;
-            if (rc == MTCP_GPU_OK && bounce) s.pend_first = first, s.pend_cnt = cnt;
+            if (rc == MTCP_GPU_OK && bounce)
+                s.pend_first = first, s.pend_cnt = cnt, s.pend_opt = opts ? opts + first : nullptr;
             first += cnt;
         }
     }
@@ -986,6 +1059,16 @@ int mtcp_gpu_rx_chunk(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len,
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     return rx_host(ctx, buf, buf_len, desc, n, off_shift, out, false, Deadline(ctx->wait_us));
+}
+
+int mtcp_gpu_rx_chunk_opts(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len,
+                           const mtcp_gpu_desc *desc, uint32_t n, uint32_t off_shift,
+                           mtcp_gpu_result *out, mtcp_gpu_tcpopt *opts) {
+    if (!ctx || (n && (!buf || !desc || !out || !opts)) || off_shift > 16) return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    return rx_host(ctx, buf, buf_len, desc, n, off_shift, out, false, Deadline(ctx->wait_us), opts);
 }
 
 int mtcp_gpu_rx_ptrs(mtcp_gpu_ctx *ctx, const uint8_t *const *pkts, const uint16_t *lens,
@@ -1121,6 +1204,42 @@ int mtcp_gpu_tx_fill(mtcp_gpu_ctx *ctx, uint8_t *buf, uint64_t buf_len, const mt
     }
     if (n_filled) *n_filled = cnt;
     return MTCP_GPU_OK;
+}
+
+// ---- TCP option records -------------------------------------
+int mtcp_gpu_rx_tcpopt_chunk_dev(mtcp_gpu_ctx *ctx, const void *d_buf, uint64_t buf_len,
+                                 const mtcp_gpu_desc *d_desc, uint32_t n, uint32_t off_shift,
+                                 const mtcp_gpu_result *d_res, mtcp_gpu_tcpopt *d_opt, void *stream) {
+    if (!ctx || (n && (!d_buf || !d_desc || !d_res || !d_opt)) || off_shift > 16 || (buf_len & 15) ||
+        ((uintptr_t)d_buf & 15) || ((uintptr_t)d_res & out_align(ctx)) || ((uintptr_t)d_desc & 7) ||
+        ((uintptr_t)d_opt & 15))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    mg::KParams kp = base_params(ctx);
+    kp.buf = static_cast<const uint8_t *>(d_buf);
+    kp.buf_len = buf_len;
+    kp.desc = d_desc;
+    kp.n = n;
+    kp.off_shift = off_shift;
+    return launch_tcpopt<false>(ctx, kp, d_res, d_opt, pick(ctx, stream));
+}
+
+int mtcp_gpu_rx_tcpopt_ptrs_dev(mtcp_gpu_ctx *ctx, const uint8_t *const *d_pkts, const uint16_t *d_lens,
+                                uint32_t n, const mtcp_gpu_result *d_res, mtcp_gpu_tcpopt *d_opt,
+                                void *stream) {
+    if (!ctx || (n && (!d_pkts || !d_lens || !d_res || !d_opt)) || ((uintptr_t)d_res & out_align(ctx)) ||
+        ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_lens & 1) || ((uintptr_t)d_opt & 15))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    mg::KParams kp = base_params(ctx);
+    kp.ptrs = d_pkts;
+    kp.lens = d_lens;
+    kp.n = n;
+    return launch_tcpopt<true>(ctx, kp, d_res, d_opt, pick(ctx, stream));
 }
 
 // ---- flow-table hash --------------------------------------

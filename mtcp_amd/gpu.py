@@ -16,7 +16,8 @@ import os
 import numpy as np
 
 from ._lib import check, lib
-from ._types import ADDR_ENTRY_DTYPE, DESC_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE
+from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
+                     TCPOPT_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -247,6 +248,31 @@ class Context:
         check(lib().mtcp_gpu_flow_hash(self._h, res.ctypes.data, len(res), bins.ctypes.data),
               "mtcp_gpu_flow_hash")
         return bins
+
+    # -- TCP option records (ParseTCPTimestamp / ParseTCPOptions, tcp_util.c:14-92) --
+    def rx_tcpopt_chunk_dev(self, buf, desc, n: int, off_shift: int, res, opt, stream=None) -> None:
+        """res: the records this context's rx call wrote for these frames;
+        opt: n x 16 B (TCPOPT_DTYPE)."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_rx_tcpopt_chunk_dev(self._h, _dptr(buf), buf.numel() * buf.element_size(),
+                                                     _dptr(desc), n, off_shift, _dptr(res), _dptr(opt),
+                                                     st), "mtcp_gpu_rx_tcpopt_chunk_dev")
+
+    def rx_tcpopt_ptrs_dev(self, ptrs, lens, n: int, res, opt, stream=None) -> None:
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_rx_tcpopt_ptrs_dev(self._h, _dptr(ptrs), _dptr(lens), n, _dptr(res),
+                                                    _dptr(opt), st), "mtcp_gpu_rx_tcpopt_ptrs_dev")
+
+    def rx_chunk_opts(self, buf: np.ndarray, desc: np.ndarray,
+                      off_shift: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """mtcp_gpu_rx_chunk_opts: rx_chunk's records and the option records."""
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        out = np.zeros(len(desc), dtype=self.result_dtype)
+        opts = np.zeros(len(desc), dtype=TCPOPT_DTYPE)
+        check(lib().mtcp_gpu_rx_chunk_opts(self._h, buf.ctypes.data, buf.nbytes, desc.ctypes.data,
+                                           len(desc), off_shift, out.ctypes.data, opts.ctypes.data),
+              "mtcp_gpu_rx_chunk_opts")
+        return out, opts
 
     # -- RSS-friendly address pool (mtcp/src/addr_pool.c:103-180) ------------
     def rss_queue_map_dev(self, saddr_base_h: int, num_addr: int, daddr_h: int, dport_h: int,
