@@ -48,6 +48,14 @@
  *       the option walks behind the flow lookup: ParseTCPTimestamp
  *       (mtcp/src/tcp_util.c:61-92, called at tcp_in.c:109) and ParseTCPOptions
  *       (tcp_util.c:14-59, called at tcp_in.c:72 and :88), one record per packet.
+ *   mtcp_gpu_steer_dev / _steer / _steer_work_bytes / _steer_tile (mtcp_gpu_steer.h)
+ *       what the queue number is for: the NIC's RSS redirection table puts each
+ *       frame into the receive ring of one core (mtcp/src/dpdk_module.c:101-121)
+ *       and each mTCP thread reads only its own ring (dpdk_module.c:401-402).
+ *       The steer calls are that step for a batch the GPU has hashed: a stable
+ *       partition of the rx records by rss_queue (GetRSSCPUCore,
+ *       mtcp/src/rss.c:90-103) into one list of packet indices per queue, in
+ *       arrival order, in place of a per-packet walk of the records on the CPU.
  *   mtcp_gpu_dev_ioctl
  *       io_module_func.dev_ioctl (mtcp/src/include/io_module.h:67) for the
  *       checksum commands PKT_RX_IP_CSUM / PKT_RX_TCP_CSUM / PKT_TX_IP_CSUM /
@@ -259,7 +267,8 @@ void mtcp_gpu_close(mtcp_gpu_ctx *ctx);
  * mtcp_gpu_rx_chunk, _rx_chunk_opts (mtcp_gpu_tcpopt.h), _rx_ptrs, _tx_fill,
  * _tx_fill_ptrs (whose _tx_fill_ptrs_for argument, when non-zero, overrides
  * the limit),
- * _flow_hash, _addr_pool_search, _reserve, _sync and _close, and the calls
+ * _flow_hash, _steer (mtcp_gpu_steer.h), _addr_pool_search, _reserve, _sync
+ * and _close, and the calls
  * of the context's rxqs (mtcp_gpu_rxq.h: create, flush, wait, destroy; an
  * rxq takes the limit its context has when it is created).
  *

@@ -48,6 +48,11 @@ assert TCPOPT_DTYPE.itemsize == 16
 TCPOPT_TS_FOUND, TCPOPT_MSS, TCPOPT_WSCALE, TCPOPT_SACK_PERMIT = 0x01, 0x02, 0x04, 0x08
 TCPOPT_SAW_TIMESTAMP, TCPOPT_TS_UNPINNED, TCPOPT_SYN_UNPINNED = 0x20, 0x40, 0x80
 
+# include/mtcp_gpu_steer.h
+STEER_MAX_QUEUES = 128
+STEER_MAX_PKTS = 1 << 26
+STEER_DROP_BAD = 0x1
+
 NUM_BINS_FLOWS = 131072      # mtcp/src/include/fhash.h:7
 FLOW_NONE = 0xFFFFFFFF
 MIN_PORT, MAX_PORT = 1025, 65536   # mtcp/src/include/addr_pool.h:7-8

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/mtcp_gpu.h"
+#include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
 #include "ctx_internal.hpp"
 #include "dispatch.hpp"
@@ -25,6 +26,7 @@
 #include "park.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
+#include "steer_kernels.hpp"
 #include "tcpopt_kernels.hpp"
 #include "wait.hpp"
 
@@ -1285,6 +1287,144 @@ int mtcp_gpu_flow_hash(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n
         rc = MTCP_GPU_EIO;
     rc = finish_call(ctx, rc, dl, 1);
     if (rc == MTCP_GPU_OK && bounce) memcpy(bins, s.h_out, bbytes);
+    return rc;
+}
+
+// ---- steering by RSS queue ----------------------------------
+namespace {
+
+static_assert(mg::kSteerMaxLists == MTCP_GPU_STEER_MAX_QUEUES + 1, "steer_kernels.hpp sizes its LDS for the ABI's Q");
+
+uint32_t steer_queues(const mtcp_gpu_ctx *ctx) { return (ctx->flags & MTCP_GPU_F_RSS) ? ctx->rss_nq : 1u; }
+
+// The workspace of a batch above one tile: the parked destination bytes, the
+// counts of every list for every wave of every tile (list-major, four waves
+// per tile) and the lists' totals, each part 16 B aligned.  A batch of one tile runs in one workgroup and uses none.
+struct SteerWork {
+    uint32_t ntiles;
+    uint64_t cnt_off, tot_off, bytes;
+};
+SteerWork steer_work(uint32_t Q, uint32_t n) {
+    SteerWork w{};
+    w.ntiles = (n + mg::kSteerTile - 1) / mg::kSteerTile;
+    if (w.ntiles <= 1) {
+        w.bytes = 16;
+        return w;
+    }
+    const uint64_t L = (uint64_t)Q + 1;
+    w.cnt_off = ((uint64_t)n + 15) & ~15ull;
+    w.tot_off = w.cnt_off + 16 * L * w.ntiles;
+    w.bytes = w.tot_off + ((4 * L + 15) & ~15ull);
+    return w;
+}
+
+}  // namespace
+
+uint32_t mtcp_gpu_steer_tile(void) { return mg::kSteerTile; }
+
+uint64_t mtcp_gpu_steer_work_bytes(const mtcp_gpu_ctx *ctx, uint32_t n) {
+    if (!ctx || n > MTCP_GPU_STEER_MAX_PKTS || steer_queues(ctx) > MTCP_GPU_STEER_MAX_QUEUES) return 0;
+    return steer_work(steer_queues(ctx), n).bytes;
+}
+
+int mtcp_gpu_steer_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, uint32_t n, uint32_t flags,
+                       uint32_t *d_idx, uint32_t *d_start, const mtcp_gpu_desc *d_desc,
+                       mtcp_gpu_desc *d_desc_out, void *d_work, uint64_t work_bytes, void *stream) {
+    if (!ctx || (flags & ~MTCP_GPU_STEER_DROP_BAD) || n > MTCP_GPU_STEER_MAX_PKTS ||
+        steer_queues(ctx) > MTCP_GPU_STEER_MAX_QUEUES || (n && (!d_res || !d_idx || !d_start || !d_work)) ||
+        (!d_desc != !d_desc_out) || ((uintptr_t)d_res & 7) || ((uintptr_t)d_idx & 3) ||
+        ((uintptr_t)d_start & 3) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_desc_out & 7) ||
+        ((uintptr_t)d_work & 15))
+        return MTCP_GPU_EINVAL;
+    const uint32_t Q = steer_queues(ctx);
+    const SteerWork w = steer_work(Q, n);
+    if (n && work_bytes < w.bytes) return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const bool cmp = ctx->flags & MTCP_GPU_F_COMPACT, gather = d_desc != nullptr;
+    const uint32_t *res = reinterpret_cast<const uint32_t *>(d_res);
+    const uint2 *desc = reinterpret_cast<const uint2 *>(d_desc);
+    uint2 *desc_out = reinterpret_cast<uint2 *>(d_desc_out);
+    const dim3 block(mg::kBlock);
+    if (w.ntiles == 1) {
+#define STEER_ONE(C, G) \
+    hipLaunchKernelGGL((mg::steer_one_kernel<C, G>), dim3(1), block, 0, st, res, n, Q, flags, d_idx, d_start, \
+                       desc, desc_out)
+        if (cmp) {
+            if (gather) STEER_ONE(true, true); else STEER_ONE(true, false);
+        } else {
+            if (gather) STEER_ONE(false, true); else STEER_ONE(false, false);
+        }
+#undef STEER_ONE
+        return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+    }
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(work + w.cnt_off);
+    uint32_t *totals = reinterpret_cast<uint32_t *>(work + w.tot_off);
+    if (cmp)
+        hipLaunchKernelGGL(mg::steer_count_kernel<true>, dim3(w.ntiles), block, 0, st, res, n, Q, flags, work,
+                           cnt, w.ntiles);
+    else
+        hipLaunchKernelGGL(mg::steer_count_kernel<false>, dim3(w.ntiles), block, 0, st, res, n, Q, flags, work,
+                           cnt, w.ntiles);
+    hipLaunchKernelGGL(mg::steer_scan_kernel, dim3(Q + 1), block, 0, st, cnt,
+                       w.ntiles * mg::kWavesPerBlock, totals);
+    if (gather)
+        hipLaunchKernelGGL(mg::steer_emit_kernel<true>, dim3(w.ntiles), block, 0, st, work, n, Q, cnt, totals,
+                           w.ntiles, d_idx, d_start, desc, desc_out);
+    else
+        hipLaunchKernelGGL(mg::steer_emit_kernel<false>, dim3(w.ntiles), block, 0, st, work, n, Q, cnt, totals,
+                           w.ntiles, d_idx, d_start, desc, desc_out);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+// Built like mtcp_gpu_flow_hash: the records go up into stage 0's record
+// buffer; its chunk buffer holds idx[n], start[Q + 2] and the workspace.
+int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, uint32_t flags,
+                   uint32_t *idx, uint32_t *start) {
+    if (!ctx || (flags & ~MTCP_GPU_STEER_DROP_BAD) || n > MTCP_GPU_STEER_MAX_PKTS ||
+        steer_queues(ctx) > MTCP_GPU_STEER_MAX_QUEUES || (n && (!res || !idx || !start)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const bool bounce = dl.bounded;
+    const uint32_t Q = steer_queues(ctx);
+    const uint64_t rbytes = (uint64_t)n * record_size(ctx), ibytes = (uint64_t)n * sizeof(uint32_t);
+    const uint64_t sbytes = ((uint64_t)Q + 2) * sizeof(uint32_t);
+    const uint64_t work_off = (ibytes + sbytes + 15) & ~15ull;
+    const uint64_t wbytes = steer_work(Q, n).bytes;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, work_off + wbytes, n, dl);
+    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, rbytes, ibytes + sbytes, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    const void *src = res;
+    if (bounce) {
+        memcpy(s.h_in, res, rbytes);
+        src = s.h_in;
+    }
+    uint32_t *d_idx = reinterpret_cast<uint32_t *>(s.d_buf);
+    uint32_t *d_start = d_idx + n;
+    if (!HIP_OK(hipMemcpyAsync(s.d_out, src, rbytes, hipMemcpyHostToDevice, s.stream)))
+        rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK)
+        rc = mtcp_gpu_steer_dev(ctx, s.d_out, n, flags, d_idx, d_start, nullptr, nullptr, s.d_buf + work_off,
+                                wbytes, s.stream);
+    if (rc == MTCP_GPU_OK && bounce &&
+        !HIP_OK(hipMemcpyAsync(s.h_out, d_idx, ibytes + sbytes, hipMemcpyDeviceToHost, s.stream)))
+        rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK && !bounce &&
+        (!HIP_OK(hipMemcpyAsync(idx, d_idx, ibytes, hipMemcpyDeviceToHost, s.stream)) ||
+         !HIP_OK(hipMemcpyAsync(start, d_start, sbytes, hipMemcpyDeviceToHost, s.stream))))
+        rc = MTCP_GPU_EIO;
+    rc = finish_call(ctx, rc, dl, 1);
+    if (rc == MTCP_GPU_OK && bounce) {
+        memcpy(idx, s.h_out, ibytes);
+        memcpy(start, s.h_out + ibytes, sbytes);
+    }
     return rc;
 }
 

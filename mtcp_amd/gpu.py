@@ -69,6 +69,8 @@ class Context:
               "mtcp_gpu_open")
         self.device = device
         self.compact = compact
+        # Q of the steer calls (mtcp_gpu_steer.h): 1 without RSS
+        self.num_queues = rss_queues if rss else 1
         # the rx records this context writes (numpy dtype of one record)
         self.result_dtype = RESULT16_DTYPE if compact else RESULT_DTYPE
 
@@ -273,6 +275,34 @@ class Context:
                                            len(desc), off_shift, out.ctypes.data, opts.ctypes.data),
               "mtcp_gpu_rx_chunk_opts")
         return out, opts
+
+    # -- steering by RSS queue (dpdk_module.c:101-121, :401-402; mtcp_gpu_steer.h) --
+    @staticmethod
+    def steer_tile() -> int:
+        return lib().mtcp_gpu_steer_tile()
+
+    def steer_work_bytes(self, n: int) -> int:
+        return lib().mtcp_gpu_steer_work_bytes(self._h, n)
+
+    def steer_dev(self, res, n: int, idx, start, work, flags: int = 0, desc=None, desc_out=None,
+                  stream=None) -> None:
+        """res: this context's rx records; idx: n x u32; start: (Q + 2) x u32;
+        work: at least steer_work_bytes(n) bytes, 16 B aligned; desc / desc_out:
+        both or neither."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_steer_dev(self._h, _dptr(res), n, flags, _dptr(idx), _dptr(start),
+                                           None if desc is None else _dptr(desc),
+                                           None if desc_out is None else _dptr(desc_out), _dptr(work),
+                                           work.numel() * work.element_size(), st), "mtcp_gpu_steer_dev")
+
+    def steer(self, res: np.ndarray, flags: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """mtcp_gpu_steer: (idx, start) of this context's records in host memory."""
+        res = np.ascontiguousarray(res, dtype=self.result_dtype)
+        idx = np.zeros(len(res), dtype=np.uint32)
+        start = np.zeros(self.num_queues + 2, dtype=np.uint32)
+        check(lib().mtcp_gpu_steer(self._h, res.ctypes.data, len(res), flags, idx.ctypes.data,
+                                   start.ctypes.data), "mtcp_gpu_steer")
+        return idx, start
 
     # -- RSS-friendly address pool (mtcp/src/addr_pool.c:103-180) ------------
     def rss_queue_map_dev(self, saddr_base_h: int, num_addr: int, daddr_h: int, dport_h: int,
