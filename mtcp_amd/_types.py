@@ -53,6 +53,29 @@ STEER_MAX_QUEUES = 128
 STEER_MAX_PKTS = 1 << 26
 STEER_DROP_BAD = 0x1
 
+# include/mtcp_gpu_txbuild.h: struct mtcp_gpu_tx_seg (one segment: the arguments
+# of SendTCPPacketStandalone, tcp_out.c:135-140, or what SendTCPPacket reads
+# from its stream) and struct mtcp_gpu_tx_link (eth_out.c:72-77)
+TX_SEG_DTYPE = np.dtype([
+    ("payload_off", "<u8"), ("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
+    ("seq", "<u4"), ("ack", "<u4"), ("ts_val", "<u4"), ("ts_ecr", "<u4"), ("window", "<u2"),
+    ("ip_id", "<u2"), ("payload_len", "<u2"), ("mss", "<u2"), ("flags", "u1"), ("form", "u1"),
+    ("wscale", "u1"), ("link", "u1"),
+])
+TX_LINK_DTYPE = np.dtype([("dst", "u1", (6,)), ("src", "u1", (6,))])
+assert TX_SEG_DTYPE.itemsize == 48 and TX_LINK_DTYPE.itemsize == 12
+assert [TX_SEG_DTYPE.fields[f][1] for f in TX_SEG_DTYPE.names] == [0, 8, 12, 16, 18, 20, 24, 28, 32, 36, 38, 40,
+                                                                   42, 44, 45, 46, 47]
+TXB_NO_CSUM = 0x1
+TXB_BUILT, TXB_BAD_SEG, TXB_BAD_DESC, TXB_BAD_PAYLOAD = 0, 1, 2, 3
+TXB_FLAG_FIN, TXB_FLAG_SYN, TXB_FLAG_RST, TXB_FLAG_PSH, TXB_FLAG_ACK = 0x01, 0x02, 0x04, 0x08, 0x10
+
+
+def tx_seg_frame_len(flags, payload_len):
+    """MTCP_GPU_TX_SEG_FRAME_LEN: 54 + optlen + payload_len (scalars or arrays)."""
+    return 54 + np.where(np.asarray(flags) & TXB_FLAG_SYN, 20, 12) + np.asarray(payload_len, dtype=np.int64)
+
+
 NUM_BINS_FLOWS = 131072      # mtcp/src/include/fhash.h:7
 FLOW_NONE = 0xFFFFFFFF
 MIN_PORT, MAX_PORT = 1025, 65536   # mtcp/src/include/addr_pool.h:7-8

@@ -202,4 +202,25 @@ inline const char *kernel_name(int sched, int big, uint64_t slot) {
     }
 }
 
+// The frame builder (txbuild_kernels.hpp) puts a group of G
+// lanes on every segment: eight lanes (eight segments per wave), a 16-lane
+// row, half a wave or a whole wave.  The choice is by the batch's average
+// payload, payload_bytes / n, as rx goes by the average slot.  Eight lanes
+// cover the five or six chunks of an ACK-sized frame in one pass.  A row
+// covers 256 B of frame per pass: segments whose 66 or 74 B of headers and
+// payload fit two passes go to rows.  An MSS frame (1 514 B, 95 chunks of 16 B) fills three
+// passes of half a wave and leaves a third of a whole wave's second pass
+// idle, and two segments per wave keep twice the loads in flight; jumbo
+// payloads stream 1 KiB per pass on a whole wave.  Measured per width by
+// tools/txbuild_bench.py.
+constexpr uint64_t kTxBuildOctUpToPayload = 48;
+constexpr uint64_t kTxBuildRowUpToPayload = 384;
+constexpr uint64_t kTxBuildHalfUpToPayload = 4096;
+inline int txbuild_group(uint64_t payload_bytes, uint32_t n) {
+    const uint64_t avg = n ? payload_bytes / n : 0;
+    return avg <= kTxBuildOctUpToPayload    ? 8
+           : avg <= kTxBuildRowUpToPayload  ? 16
+           : avg <= kTxBuildHalfUpToPayload ? 32 : 64;
+}
+
 }  // namespace

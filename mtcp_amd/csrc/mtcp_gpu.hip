@@ -19,6 +19,7 @@
 #include "../../include/mtcp_gpu.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
+#include "../../include/mtcp_gpu_txbuild.h"
 #include "ctx_internal.hpp"
 #include "dispatch.hpp"
 #include "flow_kernels.hpp"
@@ -28,6 +29,7 @@
 #include "rx_span.hpp"
 #include "steer_kernels.hpp"
 #include "tcpopt_kernels.hpp"
+#include "txbuild_kernels.hpp"
 #include "wait.hpp"
 
 namespace {
@@ -1426,6 +1428,155 @@ int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, ui
         memcpy(start, s.h_out + ibytes, sbytes);
     }
     return rc;
+}
+
+// ---- tx frames from segment records --------------------------
+namespace {
+
+static_assert(sizeof(mtcp_gpu_tx_seg) == 48 && sizeof(mtcp_gpu_tx_link) == 12, "mtcp_gpu_txbuild.h layouts");
+
+bool txbuild_args_ok(const mtcp_gpu_ctx *ctx, uint32_t n, const void *seg, const void *payload,
+                     uint64_t payload_bytes, const void *links, uint32_t n_links, const void *buf,
+                     uint64_t buf_len, const void *desc, uint32_t off_shift, uint32_t flags, const void *status) {
+    if (!ctx || (flags & ~MTCP_GPU_TXB_NO_CSUM) || off_shift > 16 || n_links < 1 ||
+        n_links > MTCP_GPU_TXB_MAX_LINKS)
+        return false;
+    if (n && (!seg || !links || !buf || !desc || !status || (!payload && payload_bytes))) return false;
+    // the builder reads the payload while it writes frames: the two ranges are apart
+    const uintptr_t p0 = (uintptr_t)payload, b0 = (uintptr_t)buf;
+    if (n && payload_bytes && buf_len && p0 < b0 + buf_len && b0 < p0 + payload_bytes) return false;
+    return true;
+}
+
+// A staging capacity for `need`: the next power of two once the present one
+// is too small (a context grows O(log n) times, not once per new
+// maximum).
+uint64_t grown(uint64_t need, uint64_t have) {
+    if (need <= have) return need;
+    uint64_t cap = 4096;
+    while (cap < need) cap <<= 1;
+    return cap;
+}
+
+}  // namespace
+
+int mtcp_gpu_tx_build_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *d_seg, uint32_t n,
+                          const void *d_payload, uint64_t payload_bytes,
+                          const mtcp_gpu_tx_link *d_links, uint32_t n_links,
+                          void *d_buf, uint64_t buf_len, const mtcp_gpu_desc *d_desc, uint32_t off_shift,
+                          uint16_t max_mss, uint32_t flags, uint8_t *d_status, void *stream) {
+    if (!txbuild_args_ok(ctx, n, d_seg, d_payload, payload_bytes, d_links, n_links, d_buf, buf_len, d_desc,
+                         off_shift, flags, d_status) ||
+        ((uintptr_t)d_seg & 7) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_links & 3))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    mg::TxBuildParams p{};
+    p.seg = d_seg;
+    p.payload = static_cast<const uint8_t *>(d_payload);
+    p.payload_bytes = payload_bytes;
+    p.links = d_links;
+    p.n_links = n_links;
+    p.n = n;
+    p.buf = static_cast<uint8_t *>(d_buf);
+    p.buf_len = buf_len;
+    p.desc = d_desc;
+    p.off_shift = off_shift;
+    p.max_mss = max_mss ? max_mss : MTCP_GPU_TXB_DEFAULT_MSS;
+    p.no_csum = flags & MTCP_GPU_TXB_NO_CSUM;
+    p.status = d_status;
+    const int group = txbuild_group(payload_bytes, n);
+    const uint32_t per_block = mg::kBlock / group;
+    const dim3 grid(std::min<uint32_t>((n + per_block - 1) / per_block, (uint32_t)ctx->num_cu * 8));
+    hipStream_t st = pick(ctx, stream);
+    if (group == 64)
+        hipLaunchKernelGGL(mg::txbuild_kernel<64>, grid, dim3(mg::kBlock), 0, st, p);
+    else if (group == 32)
+        hipLaunchKernelGGL(mg::txbuild_kernel<32>, grid, dim3(mg::kBlock), 0, st, p);
+    else if (group == 16)
+        hipLaunchKernelGGL(mg::txbuild_kernel<16>, grid, dim3(mg::kBlock), 0, st, p);
+    else
+        hipLaunchKernelGGL(mg::txbuild_kernel<8>, grid, dim3(mg::kBlock), 0, st, p);
+    ctx->last_kernel = group == 64   ? "txbuild_kernel<wave>"
+                       : group == 32 ? "txbuild_kernel<half>"
+                       : group == 16 ? "txbuild_kernel<row>" : "txbuild_kernel<oct>";
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+// Built like mtcp_gpu_tx_fill.  Stage 0's chunk buffer holds the frames'
+// image, then the payload, the records, the links and the status bytes; the
+// image is never uploaded (the builder reads no frame byte) and comes back
+// whole into pinned staging, from where only the built frames' bytes reach buf.
+int mtcp_gpu_tx_build(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *seg, uint32_t n,
+                      const void *payload, uint64_t payload_bytes,
+                      const mtcp_gpu_tx_link *links, uint32_t n_links,
+                      void *buf, uint64_t buf_len, const mtcp_gpu_desc *desc, uint32_t off_shift,
+                      uint16_t max_mss, uint32_t flags, uint8_t *status, uint32_t *n_built) {
+    if (!txbuild_args_ok(ctx, n, seg, payload, payload_bytes, links, n_links, buf, buf_len, desc, off_shift,
+                         flags, status))
+        return MTCP_GPU_EINVAL;
+    if (n_built) *n_built = 0;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const bool bounce = dl.bounded;
+    Stage &s = ctx->stage[0];
+    auto pad = [](uint64_t v) { return (v + 15) & ~15ull; };
+    const uint64_t sbytes = (uint64_t)n * sizeof(mtcp_gpu_tx_seg), lbytes = (uint64_t)n_links * sizeof(mtcp_gpu_tx_link);
+    const uint64_t dbytes = (uint64_t)n * sizeof(mtcp_gpu_desc);
+    const uint64_t pay_off = pad(buf_len), seg_off = pay_off + pad(payload_bytes), link_off = seg_off + pad(sbytes);
+    const uint64_t st_off = link_off + pad(lbytes), total = st_off + pad(n);
+    // host side: in = payload | records | links | descriptors (bounded calls), out = image | status
+    const uint64_t hin_seg = pad(payload_bytes), hin_link = hin_seg + pad(sbytes), hin_desc = hin_link + pad(lbytes);
+    const uint64_t hin_total = hin_desc + dbytes, hout_total = pay_off + n;
+    int rc = stage_reserve(ctx, s, grown(total, s.buf_cap), (uint32_t)grown(n, s.pkt_cap), dl);
+    if (rc == MTCP_GPU_OK)
+        rc = stage_host(ctx, s, bounce ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    const void *psrc = payload, *ssrc = seg, *lsrc = links, *dsrc = desc;
+    if (bounce) {
+        bounce_in(s.h_in, payload, payload_bytes);
+        memcpy(s.h_in + hin_seg, seg, sbytes);
+        memcpy(s.h_in + hin_link, links, lbytes);
+        memcpy(s.h_in + hin_desc, desc, dbytes);
+        psrc = s.h_in;
+        ssrc = s.h_in + hin_seg;
+        lsrc = s.h_in + hin_link;
+        dsrc = s.h_in + hin_desc;
+    }
+    if ((payload_bytes &&
+         !HIP_OK(hipMemcpyAsync(s.d_buf + pay_off, psrc, payload_bytes, hipMemcpyHostToDevice, s.stream))) ||
+        !HIP_OK(hipMemcpyAsync(s.d_buf + seg_off, ssrc, sbytes, hipMemcpyHostToDevice, s.stream)) ||
+        !HIP_OK(hipMemcpyAsync(s.d_buf + link_off, lsrc, lbytes, hipMemcpyHostToDevice, s.stream)) ||
+        !HIP_OK(hipMemcpyAsync(s.d_desc, dsrc, dbytes, hipMemcpyHostToDevice, s.stream)))
+        rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK)
+        rc = mtcp_gpu_tx_build_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_seg *>(s.d_buf + seg_off), n,
+                                   s.d_buf + pay_off, payload_bytes,
+                                   reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
+                                   buf_len, s.d_desc, off_shift, max_mss, flags, s.d_buf + st_off, s.stream);
+    if (rc == MTCP_GPU_OK &&
+        ((buf_len && !HIP_OK(hipMemcpyAsync(s.h_out, s.d_buf, buf_len, hipMemcpyDeviceToHost, s.stream))) ||
+         !HIP_OK(hipMemcpyAsync(s.h_out + pay_off, s.d_buf + st_off, n, hipMemcpyDeviceToHost, s.stream))))
+        rc = MTCP_GPU_EIO;
+    rc = finish_call(ctx, rc, dl, 1);
+    if (rc != MTCP_GPU_OK) return rc;
+    const uint8_t *st = s.h_out + pay_off;
+    uint8_t *out = static_cast<uint8_t *>(buf);
+    uint32_t cnt = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t off = (uint64_t)desc[i].offset << off_shift;
+        // the kernel builds only frames inside the image (checked again here)
+        if (st[i] == MTCP_GPU_TXB_BUILT && off <= buf_len && desc[i].len <= buf_len - off) {
+            memcpy(out + off, s.h_out + off, desc[i].len);
+            ++cnt;
+        }
+    }
+    memcpy(status, st, n);
+    if (n_built) *n_built = cnt;
+    return MTCP_GPU_OK;
 }
 
 // ---- RSS-friendly address pool -----------------------------

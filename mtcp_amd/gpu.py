@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     TCPOPT_DTYPE)
+                     TCPOPT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -303,6 +303,37 @@ class Context:
         check(lib().mtcp_gpu_steer(self._h, res.ctypes.data, len(res), flags, idx.ctypes.data,
                                    start.ctypes.data), "mtcp_gpu_steer")
         return idx, start
+
+    # -- tx frames from segment records (tcp_out.c:135-354; mtcp_gpu_txbuild.h) --
+    def tx_build_dev(self, seg, n: int, payload, links, buf, desc, off_shift: int, status,
+                     max_mss: int = 0, flags: int = 0, stream=None) -> None:
+        """seg: n x 48 B (TX_SEG_DTYPE); payload: the bytes payload_off points
+        into; links: 12 B entries (TX_LINK_DTYPE); buf: the frames' image, of
+        which only built frames' bytes are written; desc: the slots; status:
+        n x u8."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_tx_build_dev(self._h, _dptr(seg), n, _dptr(payload),
+                                              payload.numel() * payload.element_size(), _dptr(links),
+                                              links.numel() * links.element_size() // 12, _dptr(buf),
+                                              buf.numel() * buf.element_size(), _dptr(desc), off_shift,
+                                              max_mss, flags, _dptr(status), st), "mtcp_gpu_tx_build_dev")
+
+    def tx_build(self, seg: np.ndarray, payload: np.ndarray, links: np.ndarray, buf: np.ndarray,
+                 desc: np.ndarray, off_shift: int = 0, max_mss: int = 0, flags: int = 0,
+                 status: np.ndarray | None = None) -> tuple[np.ndarray, int]:
+        """mtcp_gpu_tx_build: builds into the host array `buf` in place;
+        returns (status, n_built)."""
+        seg = np.ascontiguousarray(seg, dtype=TX_SEG_DTYPE)
+        links = np.ascontiguousarray(links, dtype=TX_LINK_DTYPE)
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        if status is None:
+            status = np.zeros(len(seg), dtype=np.uint8)
+        cnt = ctypes.c_uint32(0)
+        check(lib().mtcp_gpu_tx_build(self._h, seg.ctypes.data, len(seg), payload.ctypes.data, payload.nbytes,
+                                      links.ctypes.data, len(links), buf.ctypes.data, buf.nbytes,
+                                      desc.ctypes.data, off_shift, max_mss, flags,
+                                      status.ctypes.data, ctypes.byref(cnt)), "mtcp_gpu_tx_build")
+        return status, cnt.value
 
     # -- RSS-friendly address pool (mtcp/src/addr_pool.c:103-180) ------------
     def rss_queue_map_dev(self, saddr_base_h: int, num_addr: int, daddr_h: int, dport_h: int,
