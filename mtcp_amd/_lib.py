@@ -28,6 +28,8 @@ EXPORTS = (
     "mtcp_gpu_rx_tcpopt_chunk_dev", "mtcp_gpu_rx_tcpopt_ptrs_dev", "mtcp_gpu_rx_chunk_opts",
     "mtcp_gpu_steer_tile", "mtcp_gpu_steer_work_bytes", "mtcp_gpu_steer_dev", "mtcp_gpu_steer",
     "mtcp_gpu_tx_build_dev", "mtcp_gpu_tx_build",
+    "mtcp_gpu_tx_segment_plan", "mtcp_gpu_tx_segment_tile", "mtcp_gpu_tx_segment_work_bytes",
+    "mtcp_gpu_tx_segment_dev", "mtcp_gpu_tx_send_dev", "mtcp_gpu_tx_send",
     "mtcp_gpu_rxq_pending", "mtcp_gpu_rxq_flush", "mtcp_gpu_rxq_flush_async", "mtcp_gpu_rxq_wait", "mtcp_gpu_rxq_wait_for", "mtcp_gpu_rxq_get", "mtcp_gpu_rxq_get16", "mtcp_gpu_rxq_frame", "mtcp_gpu_rxq_reset",
 )
 
@@ -98,6 +100,15 @@ def lib() -> ctypes.CDLL:
                                    vp], i32),
         "mtcp_gpu_tx_build": ([vp, vp, u32, vp, u64, vp, u32, vp, u64, vp, u32, ctypes.c_uint16, u32, vp,
                                ctypes.POINTER(u32)], i32),
+        "mtcp_gpu_tx_segment_plan": ([vp, u32, u64, u32, u64, u64, u32, u32, u32, ctypes.c_uint16, vp, vp], i32),
+        "mtcp_gpu_tx_segment_tile": ([], u32),
+        "mtcp_gpu_tx_segment_work_bytes": ([u32], u64),
+        "mtcp_gpu_tx_segment_dev": ([vp, vp, u32, u64, u32, u64, u64, u32, u32, ctypes.c_uint16, vp, vp, u32, vp,
+                                     vp, vp, u64, vp], i32),
+        "mtcp_gpu_tx_send_dev": ([vp, vp, u32, vp, u64, vp, u32, vp, u64, u64, u32, u32, ctypes.c_uint16, u32,
+                                  vp, vp, u32, vp, vp, vp, vp, u64, vp], i32),
+        "mtcp_gpu_tx_send": ([vp, vp, u32, vp, u64, vp, u32, vp, u64, u64, u32, u32, ctypes.c_uint16, u32,
+                              vp, u32, vp, vp, vp], i32),
         "mtcp_gpu_pktgen_dev": ([vp, u64, vp, u32, u32, u64, u64, vp], i32),
         "mtcp_gpu_rxq_create": ([ctypes.POINTER(vp), vp, u32, u64], i32),
         "mtcp_gpu_rxq_destroy": ([vp], None),

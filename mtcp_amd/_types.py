@@ -76,6 +76,24 @@ def tx_seg_frame_len(flags, payload_len):
     return 54 + np.where(np.asarray(flags) & TXB_FLAG_SYN, 20, 12) + np.asarray(payload_len, dtype=np.int64)
 
 
-NUM_BINS_FLOWS = 131072      # mtcp/src/include/fhash.h:7
+# include/mtcp_gpu_txseg.h: struct mtcp_gpu_tx_burst (one stream of the send
+# list: what FlushTCPSendingBuffer reads of it, tcp_out.c:357-449) and struct
+# mtcp_gpu_tx_burst_result
+TX_BURST_DTYPE = np.dtype([
+    ("payload_off", "<u8"), ("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
+    ("seq", "<u4"), ("ack", "<u4"), ("ts_val", "<u4"), ("ts_ecr", "<u4"), ("len", "<u4"),
+    ("in_flight", "<u4"), ("window", "<u4"), ("peer_wnd", "<u4"), ("tcp_window", "<u2"), ("ip_id", "<u2"),
+    ("mss", "<u2"), ("link", "u1"), ("rsvd0", "u1"), ("rsvd1", "<u4"),
+])
+TX_BURST_RESULT_DTYPE = np.dtype([("first_seg", "<u4"), ("n_seg", "<u4"), ("bytes", "<u4"), ("status", "u1"),
+                                  ("stop", "u1"), ("rsvd", "<u2")])
+assert TX_BURST_DTYPE.itemsize == 64 and TX_BURST_RESULT_DTYPE.itemsize == 16
+assert [TX_BURST_DTYPE.fields[f][1] for f in TX_BURST_DTYPE.names] == [0, 8, 12, 16, 18, 20, 24, 28, 32, 36, 40, 44,
+                                                                       48, 52, 54, 56, 58, 59, 60]
+TXS_OK, TXS_BAD_BURST, TXS_BAD_PAYLOAD = 0, 1, 2
+TXS_STOP_WINDOW, TXS_STOP_PEER_WINDOW, TXS_STOP_NO_ROOM = 0x1, 0x2, 0x4
+TXSEG_MAX_BURSTS, TXSEG_MAX_SEGS, TXSEG_VOID_FORM = 1 << 24, 1 << 26, 0xFF
+
+NUM_BINS_FLOWS = 131072     # mtcp/src/include/fhash.h:7
 FLOW_NONE = 0xFFFFFFFF
 MIN_PORT, MAX_PORT = 1025, 65536   # mtcp/src/include/addr_pool.h:7-8

@@ -20,6 +20,7 @@
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
 #include "../../include/mtcp_gpu_txbuild.h"
+#include "../../include/mtcp_gpu_txseg.h"
 #include "ctx_internal.hpp"
 #include "dispatch.hpp"
 #include "flow_kernels.hpp"
@@ -30,6 +31,7 @@
 #include "steer_kernels.hpp"
 #include "tcpopt_kernels.hpp"
 #include "txbuild_kernels.hpp"
+#include "txseg_kernels.hpp"
 #include "wait.hpp"
 
 namespace {
@@ -1576,6 +1578,254 @@ int mtcp_gpu_tx_build(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *seg, uint32_t n,
     }
     memcpy(status, st, n);
     if (n_built) *n_built = cnt;
+    return MTCP_GPU_OK;
+}
+
+// ---- tx segments from send bursts ----------------------------
+namespace {
+
+static_assert(sizeof(mtcp_gpu_tx_burst) == 64 && sizeof(mtcp_gpu_tx_burst_result) == 16, "mtcp_gpu_txseg.h layouts");
+static_assert(mg::kTxsegOneSegs <= MTCP_GPU_TXSEG_MAX_SEGS, "the one-workgroup form is a seg_cap the ABI allows");
+
+// What the host plan and the device calls refuse alike.
+bool txseg_geom_ok(uint32_t n_burst, uint32_t n_links, uint64_t buf_off, uint32_t off_shift, uint32_t slot_bytes,
+                   uint32_t seg_cap) {
+    if (off_shift > 16 || n_links < 1 || n_links > MTCP_GPU_TXB_MAX_LINKS || seg_cap == 0 ||
+        seg_cap > MTCP_GPU_TXSEG_MAX_SEGS || n_burst > MTCP_GPU_TXSEG_MAX_BURSTS)
+        return false;
+    const uint64_t A = off_shift ? 1ull << off_shift : 2ull;
+    return (slot_bytes & (A - 1)) == 0 && (buf_off & (A - 1)) == 0;
+}
+
+// The workspace: the parked plans (16 B each), first[n] (u32), boff[n] (u64),
+// the plan workgroups' sums (u32 and u64 each) and the totals, each part 16 B
+// aligned.
+struct TxSegWork {
+    uint32_t nwg;
+    uint64_t first_off, boff_off, pc_off, pb_off, tot_off, bytes;
+};
+TxSegWork txseg_work(uint32_t n) {
+    auto pad = [](uint64_t v) { return (v + 15) & ~15ull; };
+    TxSegWork w{};
+    w.nwg = (n + mg::kTxsegTile - 1) / mg::kTxsegTile;
+    w.first_off = 16ull * n;
+    w.boff_off = w.first_off + pad(4ull * n);
+    w.pc_off = w.boff_off + pad(8ull * n);
+    w.pb_off = w.pc_off + pad(4ull * w.nwg);
+    w.tot_off = w.pb_off + pad(8ull * w.nwg);
+    w.bytes = w.tot_off + 16;
+    return w;
+}
+
+bool txseg_dev_args_ok(const mtcp_gpu_ctx *ctx, const void *d_burst, uint32_t n_burst, uint32_t n_links,
+                       uint64_t buf_off, uint32_t off_shift, uint32_t slot_bytes, const void *d_seg,
+                       const void *d_desc, uint32_t seg_cap, const void *d_res, const void *d_total,
+                       const void *d_work, uint64_t work_bytes) {
+    if (!ctx || !txseg_geom_ok(n_burst, n_links, buf_off, off_shift, slot_bytes, seg_cap)) return false;
+    if (!d_seg || !d_desc || !d_total || !d_work || (n_burst && (!d_burst || !d_res))) return false;
+    if (((uintptr_t)d_burst & 7) || ((uintptr_t)d_seg & 7) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_res & 7) ||
+        ((uintptr_t)d_total & 7) || ((uintptr_t)d_work & 15))
+        return false;
+    return work_bytes >= txseg_work(n_burst).bytes;
+}
+
+}  // namespace
+
+int mtcp_gpu_tx_segment_plan(const mtcp_gpu_tx_burst *burst, uint32_t n_burst, uint64_t payload_bytes,
+                             uint32_t n_links, uint64_t buf_off, uint64_t buf_len, uint32_t off_shift,
+                             uint32_t slot_bytes, uint32_t seg_cap, uint16_t max_mss,
+                             mtcp_gpu_tx_burst_result *res, uint64_t total[2]) {
+    if (!txseg_geom_ok(n_burst, n_links, buf_off, off_shift, slot_bytes, seg_cap) || !total ||
+        (n_burst && (!burst || !res)))
+        return MTCP_GPU_EINVAL;
+    const mg::TxSegParams P =
+        mg::txseg_params(payload_bytes, n_links, buf_off, buf_len, off_shift, slot_bytes, seg_cap, max_mss);
+    uint32_t S = 0, T = 0;             // the planned prefix (saturating, as on the device), the emitted total
+    uint64_t B = 0, used = 0;
+    bool cut = false;
+    for (uint32_t i = 0; i < n_burst; ++i) {
+        uint32_t w[16];
+        memcpy(w, &burst[i], sizeof w);
+        const mg::TxPlan pl = mg::txseg_plan(mg::txseg_unpack(w), P);
+        const mg::TxEmit em = mg::txseg_emitted(pl, S, B, P);
+        uint32_t r[4];
+        mg::txseg_result(pl, em, cut ? T : S, r);
+        memcpy(&res[i], r, sizeof r);
+        if (!cut) {
+            T = S + em.n;
+            used = B + em.slot_sum;
+            cut = em.n < pl.count;
+        }
+        S = mg::txseg_add_c(S, pl.count < seg_cap ? pl.count : seg_cap, seg_cap);
+        B = mg::txseg_add_b(B, pl.slot_sum);
+    }
+    total[0] = T;
+    total[1] = used;
+    return MTCP_GPU_OK;
+}
+
+uint32_t mtcp_gpu_tx_segment_tile(void) { return mg::kTxsegTile; }
+
+uint64_t mtcp_gpu_tx_segment_work_bytes(uint32_t n_burst) {
+    return n_burst > MTCP_GPU_TXSEG_MAX_BURSTS ? 0 : txseg_work(n_burst).bytes;
+}
+
+int mtcp_gpu_tx_segment_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *d_burst, uint32_t n_burst,
+                            uint64_t payload_bytes, uint32_t n_links, uint64_t buf_off, uint64_t buf_len,
+                            uint32_t off_shift, uint32_t slot_bytes, uint16_t max_mss,
+                            mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc, uint32_t seg_cap,
+                            mtcp_gpu_tx_burst_result *d_res, uint64_t *d_total,
+                            void *d_work, uint64_t work_bytes, void *stream) {
+    if (!txseg_dev_args_ok(ctx, d_burst, n_burst, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc, seg_cap,
+                           d_res, d_total, d_work, work_bytes))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const mg::TxSegParams P =
+        mg::txseg_params(payload_bytes, n_links, buf_off, buf_len, off_shift, slot_bytes, seg_cap, max_mss);
+    const dim3 block(mg::kBlock);
+    if (n_burst <= mg::kTxsegTile && seg_cap <= mg::kTxsegOneSegs) {
+        hipLaunchKernelGGL(mg::txseg_one_kernel, dim3(1), dim3(mg::kTxsegOneBlock), 0, st, d_burst, n_burst, P, d_seg, d_desc, d_res,
+                           d_total);
+        ctx->last_kernel = "txseg_one_kernel";
+        return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+    }
+    const TxSegWork w = txseg_work(n_burst);
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    mg::v4u *park = reinterpret_cast<mg::v4u *>(work);
+    uint32_t *first = reinterpret_cast<uint32_t *>(work + w.first_off);
+    uint64_t *boff = reinterpret_cast<uint64_t *>(work + w.boff_off);
+    uint32_t *part_c = reinterpret_cast<uint32_t *>(work + w.pc_off);
+    uint64_t *part_b = reinterpret_cast<uint64_t *>(work + w.pb_off);
+    unsigned long long *tot_b = reinterpret_cast<unsigned long long *>(work + w.tot_off);
+    uint32_t *tot_c = reinterpret_cast<uint32_t *>(work + w.tot_off + 8);
+    if (n_burst) {
+        hipLaunchKernelGGL(mg::txseg_plan_kernel, dim3(w.nwg), block, 0, st, d_burst, n_burst, P, park, part_c,
+                           part_b);
+        hipLaunchKernelGGL(mg::txseg_scan_kernel, dim3(1), block, 0, st, part_c, part_b, w.nwg, seg_cap, tot_c,
+                           tot_b);
+        hipLaunchKernelGGL(mg::txseg_place_kernel, dim3(w.nwg), block, 0, st, park, n_burst, P, part_c, part_b,
+                           first, boff, d_res, tot_c, tot_b);
+    }
+    const uint32_t etiles = (seg_cap + mg::kTxsegEmitTile - 1) / mg::kTxsegEmitTile;
+    hipLaunchKernelGGL(mg::txseg_emit_kernel, dim3(etiles), block, 0, st, d_burst, n_burst, P, first, boff, tot_c,
+                       tot_b, d_seg, d_desc, d_res, d_total);
+    ctx->last_kernel = "txseg_emit_kernel";
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+int mtcp_gpu_tx_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *d_burst, uint32_t n_burst,
+                         const void *d_payload, uint64_t payload_bytes,
+                         const mtcp_gpu_tx_link *d_links, uint32_t n_links,
+                         void *d_buf, uint64_t buf_off, uint64_t buf_len, uint32_t off_shift,
+                         uint32_t slot_bytes, uint16_t max_mss, uint32_t flags,
+                         mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc, uint32_t seg_cap,
+                         mtcp_gpu_tx_burst_result *d_res, uint64_t *d_total, uint8_t *d_status,
+                         void *d_work, uint64_t work_bytes, void *stream) {
+    // both calls' checks before either launches
+    if (!txseg_dev_args_ok(ctx, d_burst, n_burst, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc, seg_cap,
+                           d_res, d_total, d_work, work_bytes) ||
+        !txbuild_args_ok(ctx, seg_cap, d_seg, d_payload, payload_bytes, d_links, n_links, d_buf, buf_len, d_desc,
+                         off_shift, flags, d_status) ||
+        ((uintptr_t)d_links & 3))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    const int rc = mtcp_gpu_tx_segment_dev(ctx, d_burst, n_burst, payload_bytes, n_links, buf_off, buf_len, off_shift,
+                                           slot_bytes, max_mss, d_seg, d_desc, seg_cap, d_res, d_total, d_work,
+                                           work_bytes, stream);
+    if (rc != MTCP_GPU_OK) return rc;
+    return mtcp_gpu_tx_build_dev(ctx, d_seg, seg_cap, d_payload, payload_bytes, d_links, n_links, d_buf, buf_len,
+                                 d_desc, off_shift, max_mss, flags, d_status, stream);
+}
+
+// Built like mtcp_gpu_tx_build.  Stage 0's chunk buffer holds the frames'
+// image, then the payload, the bursts, the links, the segment records, the
+// descriptors, the status bytes, the results, the totals and the workspace;
+// the image is never uploaded and comes back whole into pinned staging with
+// the descriptors, status bytes, results and totals behind it, from where only
+// the built frames' bytes reach buf.
+int mtcp_gpu_tx_send(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *burst, uint32_t n_burst,
+                     const void *payload, uint64_t payload_bytes,
+                     const mtcp_gpu_tx_link *links, uint32_t n_links,
+                     void *buf, uint64_t buf_off, uint64_t buf_len, uint32_t off_shift,
+                     uint32_t slot_bytes, uint16_t max_mss, uint32_t flags,
+                     mtcp_gpu_desc *desc, uint32_t seg_cap, mtcp_gpu_tx_burst_result *res,
+                     uint64_t total[2], uint8_t *status) {
+    if (!ctx || !txseg_geom_ok(n_burst, n_links, buf_off, off_shift, slot_bytes, seg_cap) || !total ||
+        (n_burst && (!burst || !res)) ||
+        !txbuild_args_ok(ctx, seg_cap, desc, payload, payload_bytes, links, n_links, buf, buf_len, desc, off_shift,
+                         flags, status))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const bool bounce = dl.bounded;
+    Stage &s = ctx->stage[0];
+    auto pad = [](uint64_t v) { return (v + 15) & ~15ull; };
+    const uint64_t bbytes = (uint64_t)n_burst * sizeof(mtcp_gpu_tx_burst);
+    const uint64_t lbytes = (uint64_t)n_links * sizeof(mtcp_gpu_tx_link);
+    const uint64_t sbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_tx_seg);
+    const uint64_t dbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_desc);
+    const uint64_t rbytes = (uint64_t)n_burst * sizeof(mtcp_gpu_tx_burst_result);
+    const uint64_t wbytes = txseg_work(n_burst).bytes;
+    // device: image | payload | bursts | links | records | [descriptors | status | results | totals] | workspace
+    const uint64_t pay_off = pad(buf_len), burst_off = pay_off + pad(payload_bytes), link_off = burst_off + pad(bbytes);
+    const uint64_t seg_off = link_off + pad(lbytes), desc_off = seg_off + pad(sbytes);
+    const uint64_t st_off = desc_off + pad(dbytes), res_off = st_off + pad(seg_cap), tot_off = res_off + pad(rbytes);
+    const uint64_t work_off = tot_off + 16, dev_total = work_off + wbytes;
+    const uint64_t back = work_off - desc_off;                   // the bracketed part comes back in one copy
+    // host side: in = payload | bursts | links (bounded calls), out = image | the bracketed part
+    const uint64_t hin_burst = pad(payload_bytes), hin_link = hin_burst + pad(bbytes), hin_total = hin_link + pad(lbytes);
+    const uint64_t hout_total = pay_off + back;
+    int rc = stage_reserve(ctx, s, grown(dev_total, s.buf_cap), 0, dl);
+    if (rc == MTCP_GPU_OK)
+        rc = stage_host(ctx, s, bounce ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    const void *psrc = payload, *bsrc = burst, *lsrc = links;
+    if (bounce) {
+        bounce_in(s.h_in, payload, payload_bytes);
+        if (bbytes) memcpy(s.h_in + hin_burst, burst, bbytes);
+        memcpy(s.h_in + hin_link, links, lbytes);
+        psrc = s.h_in;
+        bsrc = s.h_in + hin_burst;
+        lsrc = s.h_in + hin_link;
+    }
+    if ((payload_bytes &&
+         !HIP_OK(hipMemcpyAsync(s.d_buf + pay_off, psrc, payload_bytes, hipMemcpyHostToDevice, s.stream))) ||
+        (bbytes && !HIP_OK(hipMemcpyAsync(s.d_buf + burst_off, bsrc, bbytes, hipMemcpyHostToDevice, s.stream))) ||
+        !HIP_OK(hipMemcpyAsync(s.d_buf + link_off, lsrc, lbytes, hipMemcpyHostToDevice, s.stream)))
+        rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK)
+        rc = mtcp_gpu_tx_send_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_burst *>(s.d_buf + burst_off), n_burst,
+                                  s.d_buf + pay_off, payload_bytes,
+                                  reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
+                                  buf_off, buf_len, off_shift, slot_bytes, max_mss, flags,
+                                  reinterpret_cast<mtcp_gpu_tx_seg *>(s.d_buf + seg_off),
+                                  reinterpret_cast<mtcp_gpu_desc *>(s.d_buf + desc_off), seg_cap,
+                                  reinterpret_cast<mtcp_gpu_tx_burst_result *>(s.d_buf + res_off),
+                                  reinterpret_cast<uint64_t *>(s.d_buf + tot_off), s.d_buf + st_off,
+                                  s.d_buf + work_off, wbytes, s.stream);
+    if (rc == MTCP_GPU_OK &&
+        ((buf_len && !HIP_OK(hipMemcpyAsync(s.h_out, s.d_buf, buf_len, hipMemcpyDeviceToHost, s.stream))) ||
+         !HIP_OK(hipMemcpyAsync(s.h_out + pay_off, s.d_buf + desc_off, back, hipMemcpyDeviceToHost, s.stream))))
+        rc = MTCP_GPU_EIO;
+    rc = finish_call(ctx, rc, dl, 1);
+    if (rc != MTCP_GPU_OK) return rc;
+    const uint8_t *hb = s.h_out + pay_off;
+    const mtcp_gpu_desc *hd = reinterpret_cast<const mtcp_gpu_desc *>(hb);
+    const uint8_t *hs = hb + (st_off - desc_off);
+    uint8_t *out = static_cast<uint8_t *>(buf);
+    for (uint32_t k = 0; k < seg_cap; ++k) {
+        const uint64_t off = (uint64_t)hd[k].offset << off_shift;
+        // the kernel builds only frames inside the image (checked again here)
+        if (hs[k] == MTCP_GPU_TXB_BUILT && off <= buf_len && hd[k].len <= buf_len - off)
+            memcpy(out + off, s.h_out + off, hd[k].len);
+    }
+    memcpy(desc, hd, dbytes);
+    memcpy(status, hs, seg_cap);
+    if (rbytes) memcpy(res, hb + (res_off - desc_off), rbytes);
+    memcpy(total, hb + (tot_off - desc_off), 16);
     return MTCP_GPU_OK;
 }
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     TCPOPT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -334,6 +334,75 @@ class Context:
                                       desc.ctypes.data, off_shift, max_mss, flags,
                                       status.ctypes.data, ctypes.byref(cnt)), "mtcp_gpu_tx_build")
         return status, cnt.value
+
+    # -- tx segments from send bursts (tcp_out.c:357-449, :587-674; mtcp_gpu_txseg.h) --
+    @staticmethod
+    def tx_segment_tile() -> int:
+        return lib().mtcp_gpu_tx_segment_tile()
+
+    @staticmethod
+    def tx_segment_work_bytes(n_burst: int) -> int:
+        return lib().mtcp_gpu_tx_segment_work_bytes(n_burst)
+
+    @staticmethod
+    def tx_segment_plan(burst: np.ndarray, payload_bytes: int, n_links: int, buf_off: int, buf_len: int,
+                        off_shift: int, slot_bytes: int, seg_cap: int,
+                        max_mss: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """mtcp_gpu_tx_segment_plan (host only, no GPU): (results, total[2])."""
+        burst = np.ascontiguousarray(burst, dtype=TX_BURST_DTYPE)
+        res = np.zeros(len(burst), dtype=TX_BURST_RESULT_DTYPE)
+        total = np.zeros(2, dtype=np.uint64)
+        check(lib().mtcp_gpu_tx_segment_plan(burst.ctypes.data, len(burst), payload_bytes, n_links, buf_off,
+                                             buf_len, off_shift, slot_bytes, seg_cap, max_mss, res.ctypes.data,
+                                             total.ctypes.data), "mtcp_gpu_tx_segment_plan")
+        return res, total
+
+    def tx_segment_dev(self, burst, n_burst: int, payload_bytes: int, n_links: int, buf_off: int, buf_len: int,
+                       off_shift: int, slot_bytes: int, seg, desc, seg_cap: int, res, total, work,
+                       max_mss: int = 0, stream=None) -> None:
+        """burst: n_burst x 64 B (TX_BURST_DTYPE); seg: seg_cap x 48 B; desc:
+        seg_cap x 8 B; res: n_burst x 16 B (TX_BURST_RESULT_DTYPE); total:
+        2 x u64; work: at least tx_segment_work_bytes(n_burst) bytes, 16 B aligned."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_tx_segment_dev(self._h, _dptr(burst), n_burst, payload_bytes, n_links, buf_off,
+                                                buf_len, off_shift, slot_bytes, max_mss, _dptr(seg), _dptr(desc),
+                                                seg_cap, _dptr(res), _dptr(total), _dptr(work),
+                                                work.numel() * work.element_size(), st),
+                  "mtcp_gpu_tx_segment_dev")
+
+    def tx_send_dev(self, burst, n_burst: int, payload, links, buf, buf_off: int, off_shift: int,
+                    slot_bytes: int, seg, desc, seg_cap: int, res, total, status, work,
+                    max_mss: int = 0, flags: int = 0, stream=None) -> None:
+        """tx_segment_dev, then tx_build_dev over all seg_cap records, on one stream."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_tx_send_dev(self._h, _dptr(burst), n_burst, _dptr(payload),
+                                             payload.numel() * payload.element_size(), _dptr(links),
+                                             links.numel() * links.element_size() // 12, _dptr(buf), buf_off,
+                                             buf.numel() * buf.element_size(), off_shift, slot_bytes, max_mss,
+                                             flags, _dptr(seg), _dptr(desc), seg_cap, _dptr(res), _dptr(total),
+                                             _dptr(status), _dptr(work), work.numel() * work.element_size(), st),
+                  "mtcp_gpu_tx_send_dev")
+
+    def tx_send(self, burst: np.ndarray, payload: np.ndarray, links: np.ndarray, buf: np.ndarray,
+                seg_cap: int, buf_off: int = 0, off_shift: int = 0, slot_bytes: int = 0, max_mss: int = 0,
+                flags: int = 0, desc: np.ndarray | None = None, res: np.ndarray | None = None,
+                status: np.ndarray | None = None):
+        """mtcp_gpu_tx_send: builds into the host array `buf` in place;
+        returns (desc, res, total, status)."""
+        burst = np.ascontiguousarray(burst, dtype=TX_BURST_DTYPE)
+        links = np.ascontiguousarray(links, dtype=TX_LINK_DTYPE)
+        if desc is None:
+            desc = np.zeros(seg_cap, dtype=DESC_DTYPE)
+        if res is None:
+            res = np.zeros(len(burst), dtype=TX_BURST_RESULT_DTYPE)
+        if status is None:
+            status = np.zeros(seg_cap, dtype=np.uint8)
+        total = np.zeros(2, dtype=np.uint64)
+        check(lib().mtcp_gpu_tx_send(self._h, burst.ctypes.data, len(burst), payload.ctypes.data, payload.nbytes,
+                                     links.ctypes.data, len(links), buf.ctypes.data, buf_off, buf.nbytes,
+                                     off_shift, slot_bytes, max_mss, flags, desc.ctypes.data, seg_cap,
+                                     res.ctypes.data, total.ctypes.data, status.ctypes.data), "mtcp_gpu_tx_send")
+        return desc, res, total, status
 
     # -- RSS-friendly address pool (mtcp/src/addr_pool.c:103-180) ------------
     def rss_queue_map_dev(self, saddr_base_h: int, num_addr: int, daddr_h: int, dport_h: int,
