@@ -56,6 +56,13 @@
  *       partition of the rx records by rss_queue (GetRSSCPUCore,
  *       mtcp/src/rss.c:90-103) into one list of packet indices per queue, in
  *       arrival order, in place of a per-packet walk of the records on the CPU.
+ *   mtcp_gpu_flowtab_create / _destroy / _update[_dev] / _lookup[_dev] / _stats /
+ *   _rehash / _home / _capacity (mtcp_gpu_flowtab.h)
+ *       the step behind the bin: StreamHTSearch (mtcp/src/tcp_in.c:1181-1186,
+ *       mtcp/src/fhash.c:103-121) for a whole batch against a device-resident
+ *       mirror of the flow table, which the caller keeps in step with batched
+ *       StreamHTInsert / StreamHTRemove deltas (fhash.c:68-101): one stream id,
+ *       a miss or "never reaches the table" per record.
  *   mtcp_gpu_dev_ioctl
  *       io_module_func.dev_ioctl (mtcp/src/include/io_module.h:67) for the
  *       checksum commands PKT_RX_IP_CSUM / PKT_RX_TCP_CSUM / PKT_TX_IP_CSUM /
@@ -267,8 +274,9 @@ void mtcp_gpu_close(mtcp_gpu_ctx *ctx);
  * mtcp_gpu_rx_chunk, _rx_chunk_opts (mtcp_gpu_tcpopt.h), _rx_ptrs, _tx_fill,
  * _tx_fill_ptrs (whose _tx_fill_ptrs_for argument, when non-zero, overrides
  * the limit),
- * _flow_hash, _steer (mtcp_gpu_steer.h), _addr_pool_search, _reserve, _sync
- * and _close, and the calls
+ * _flow_hash, _steer (mtcp_gpu_steer.h), _flowtab_create, _flowtab_update,
+ * _flowtab_lookup, _flowtab_stats and _flowtab_rehash (mtcp_gpu_flowtab.h),
+ * _addr_pool_search, _reserve, _sync and _close, and the calls
  * of the context's rxqs (mtcp_gpu_rxq.h: create, flush, wait, destroy; an
  * rxq takes the limit its context has when it is created).
  *

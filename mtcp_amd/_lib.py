@@ -30,6 +30,9 @@ EXPORTS = (
     "mtcp_gpu_tx_build_dev", "mtcp_gpu_tx_build",
     "mtcp_gpu_tx_segment_plan", "mtcp_gpu_tx_segment_tile", "mtcp_gpu_tx_segment_work_bytes",
     "mtcp_gpu_tx_segment_dev", "mtcp_gpu_tx_send_dev", "mtcp_gpu_tx_send",
+    "mtcp_gpu_flowtab_home", "mtcp_gpu_flowtab_create", "mtcp_gpu_flowtab_destroy", "mtcp_gpu_flowtab_capacity",
+    "mtcp_gpu_flowtab_update_dev", "mtcp_gpu_flowtab_lookup_dev", "mtcp_gpu_flowtab_update",
+    "mtcp_gpu_flowtab_lookup", "mtcp_gpu_flowtab_stats", "mtcp_gpu_flowtab_rehash",
     "mtcp_gpu_rxq_pending", "mtcp_gpu_rxq_flush", "mtcp_gpu_rxq_flush_async", "mtcp_gpu_rxq_wait", "mtcp_gpu_rxq_wait_for", "mtcp_gpu_rxq_get", "mtcp_gpu_rxq_get16", "mtcp_gpu_rxq_frame", "mtcp_gpu_rxq_reset",
 )
 
@@ -109,6 +112,16 @@ def lib() -> ctypes.CDLL:
                                   vp, vp, u32, vp, vp, vp, vp, u64, vp], i32),
         "mtcp_gpu_tx_send": ([vp, vp, u32, vp, u64, vp, u32, vp, u64, u64, u32, u32, ctypes.c_uint16, u32,
                               vp, u32, vp, vp, vp], i32),
+        "mtcp_gpu_flowtab_home": ([vp, u32], u32),
+        "mtcp_gpu_flowtab_create": ([vp, u32, ctypes.POINTER(vp)], i32),
+        "mtcp_gpu_flowtab_destroy": ([vp], None),
+        "mtcp_gpu_flowtab_capacity": ([vp], u32),
+        "mtcp_gpu_flowtab_update_dev": ([vp, vp, u32, vp, u32, vp], i32),
+        "mtcp_gpu_flowtab_lookup_dev": ([vp, vp, u32, vp, vp, vp], i32),
+        "mtcp_gpu_flowtab_update": ([vp, vp, u32, vp, u32], i32),
+        "mtcp_gpu_flowtab_lookup": ([vp, vp, u32, vp, vp], i32),
+        "mtcp_gpu_flowtab_stats": ([vp, vp], i32),
+        "mtcp_gpu_flowtab_rehash": ([vp], i32),
         "mtcp_gpu_pktgen_dev": ([vp, u64, vp, u32, u32, u64, u64, vp], i32),
         "mtcp_gpu_rxq_create": ([ctypes.POINTER(vp), vp, u32, u64], i32),
         "mtcp_gpu_rxq_destroy": ([vp], None),

@@ -96,4 +96,15 @@ TXSEG_MAX_BURSTS, TXSEG_MAX_SEGS, TXSEG_VOID_FORM = 1 << 24, 1 << 26, 0xFF
 
 NUM_BINS_FLOWS = 131072     # mtcp/src/include/fhash.h:7
 FLOW_NONE = 0xFFFFFFFF
+
+# include/mtcp_gpu_flowtab.h: struct mtcp_gpu_flow_entry (the 12 key bytes
+# HashFlow reads, tcp_stream.c:56-90, in the stream's orientation, and the
+# caller's stream number) and struct mtcp_gpu_flowtab_counters
+FLOW_ENTRY_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"), ("id", "<u4")])
+FLOWTAB_COUNTERS_DTYPE = np.dtype([("live", "<u4"), ("tombs", "<u4"), ("insert_failed", "<u4"),
+                                   ("remove_missed", "<u4")])
+assert FLOW_ENTRY_DTYPE.itemsize == 16 and FLOWTAB_COUNTERS_DTYPE.itemsize == 16
+FLOW_MISS = 0xFFFFFFFE
+FLOWTAB_MAX_ID = 0xFFFFFFEF
+FLOWTAB_MIN_CAP_LOG2, FLOWTAB_MAX_CAP_LOG2, FLOWTAB_MAX_BATCH = 4, 26, 1 << 26
 MIN_PORT, MAX_PORT = 1025, 65536   # mtcp/src/include/addr_pool.h:7-8

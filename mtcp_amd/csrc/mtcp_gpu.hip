@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/mtcp_gpu.h"
+#include "../../include/mtcp_gpu_flowtab.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
 #include "../../include/mtcp_gpu_txbuild.h"
@@ -24,6 +25,7 @@
 #include "ctx_internal.hpp"
 #include "dispatch.hpp"
 #include "flow_kernels.hpp"
+#include "flowtab_kernels.hpp"
 #include "host_copy.hpp"
 #include "park.hpp"
 #include "rx_kernels.hpp"
@@ -1429,6 +1431,254 @@ int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, ui
         memcpy(idx, s.h_out, ibytes);
         memcpy(start, s.h_out + ibytes, sbytes);
     }
+    return rc;
+}
+
+// ---- device flow table ----------------------------------------
+}  // extern "C"
+
+// The mirror of one tcp_flow_table (fhash.c:16-56).  Bound to its context:
+// it is created, destroyed and used through that context's device, stream and
+// wait limit.
+struct mtcp_gpu_flowtab {
+    mtcp_gpu_ctx *ctx = nullptr;
+    uint32_t cap_log2 = 0;
+    uint4 *slots = nullptr;              // 2^cap_log2 of them (park.hpp)
+    uint32_t *stats = nullptr;           // mtcp_gpu_flowtab_counters on the device
+    mtcp_gpu_flowtab_counters *h_stats = nullptr;   // pinned, for the bounded stats call
+};
+
+namespace {
+
+static_assert(sizeof(mtcp_gpu_flow_entry) == 16 && sizeof(mtcp_gpu_flowtab_counters) == 16,
+              "mtcp_gpu_flowtab.h layouts");
+static_assert(MTCP_GPU_FLOWTAB_MIN_CAP_LOG2 >= 2, "flowtab_lookup_kernel<4> walks the slots four at a time");
+
+// slots loaded per probe step of the lookup (flowtab_kernels.hpp)
+constexpr int kFlowtabGroup = 4;
+
+size_t flowtab_bytes(const mtcp_gpu_flowtab *t) { return sizeof(uint4) << t->cap_log2; }
+uint32_t flowtab_mask(const mtcp_gpu_flowtab *t) { return (1u << t->cap_log2) - 1; }
+
+// one lane per entry or slot, up to 8 workgroups per CU, grid-stride beyond
+dim3 flowtab_grid(const mtcp_gpu_ctx *ctx, uint32_t n) {
+    return dim3(std::max(1u, std::min<uint32_t>((n + mg::kBlock - 1) / mg::kBlock, (uint32_t)ctx->num_cu * 8)));
+}
+
+bool flowtab_ids_ok(const mtcp_gpu_flow_entry *e, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (e[i].id > MTCP_GPU_FLOWTAB_MAX_ID) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t mtcp_gpu_flowtab_home(const void *key12, uint32_t cap_log2) {
+    if (!key12 || cap_log2 < MTCP_GPU_FLOWTAB_MIN_CAP_LOG2 || cap_log2 > MTCP_GPU_FLOWTAB_MAX_CAP_LOG2)
+        return 0xFFFFFFFFu;
+    uint32_t key[3];
+    memcpy(key, key12, 12);
+    return mg::flowtab_home(key, (1u << cap_log2) - 1);
+}
+
+int mtcp_gpu_flowtab_create(mtcp_gpu_ctx *ctx, uint32_t cap_log2, mtcp_gpu_flowtab **tab) {
+    if (tab) *tab = nullptr;
+    if (!ctx || !tab || cap_log2 < MTCP_GPU_FLOWTAB_MIN_CAP_LOG2 || cap_log2 > MTCP_GPU_FLOWTAB_MAX_CAP_LOG2)
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    if (!dg.ok) return MTCP_GPU_ENODEV;
+    mtcp_gpu_flowtab *t = new (std::nothrow) mtcp_gpu_flowtab;
+    if (!t) return MTCP_GPU_ENOMEM;
+    t->ctx = ctx;
+    t->cap_log2 = cap_log2;
+    const Deadline dl(ctx->wait_us);
+    int rc = MTCP_GPU_OK;
+    if (!HIP_OK(mtcp_park::alloc(&t->slots, flowtab_bytes(t), mtcp_park::kDevice)) ||
+        !HIP_OK(mtcp_park::alloc(&t->stats, 16, mtcp_park::kDevice)) ||
+        !HIP_OK(mtcp_park::alloc(&t->h_stats, 16, mtcp_park::kHost)))
+        rc = MTCP_GPU_ENOMEM;
+    // every slot EMPTY (all bytes 0xFF), every counter 0
+    if (rc == MTCP_GPU_OK && (!HIP_OK(hipMemsetAsync(t->slots, 0xFF, flowtab_bytes(t), ctx->stream)) ||
+                              !HIP_OK(hipMemsetAsync(t->stats, 0, 16, ctx->stream))))
+        rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK) rc = waited(ctx, drain(ctx->stream, dl));
+    if (rc != MTCP_GPU_OK) {
+        if (rc != MTCP_GPU_ETIMEDOUT) {          // past the limit the clears may still run: the buffers stay
+            mtcp_park::release(t->slots, flowtab_bytes(t), mtcp_park::kDevice, !dl.bounded);
+            mtcp_park::release(t->stats, 16, mtcp_park::kDevice, !dl.bounded);
+            mtcp_park::release(t->h_stats, 16, mtcp_park::kHost, !dl.bounded);
+        }
+        delete t;
+        return rc;
+    }
+    *tab = t;
+    return MTCP_GPU_OK;
+}
+
+void mtcp_gpu_flowtab_destroy(mtcp_gpu_flowtab *tab) {
+    if (!tab) return;
+    if (!tab->ctx->abandoned) {                  // abandoned: work given up on may still use the buffers
+        DeviceGuard dg(tab->ctx->device);
+        const bool may_free = tab->ctx->wait_us == 0;
+        mtcp_park::release(tab->slots, flowtab_bytes(tab), mtcp_park::kDevice, may_free);
+        mtcp_park::release(tab->stats, 16, mtcp_park::kDevice, may_free);
+        mtcp_park::release(tab->h_stats, 16, mtcp_park::kHost, may_free);
+    }
+    delete tab;
+}
+
+uint32_t mtcp_gpu_flowtab_capacity(const mtcp_gpu_flowtab *tab) { return tab ? 1u << tab->cap_log2 : 0u; }
+
+int mtcp_gpu_flowtab_update_dev(mtcp_gpu_flowtab *tab, const mtcp_gpu_flow_entry *d_del, uint32_t n_del,
+                                const mtcp_gpu_flow_entry *d_ins, uint32_t n_ins, void *stream) {
+    if (!tab || (n_del && !d_del) || (n_ins && !d_ins) || ((uintptr_t)d_del & 15) || ((uintptr_t)d_ins & 15) ||
+        n_del > MTCP_GPU_FLOWTAB_MAX_BATCH || n_ins > MTCP_GPU_FLOWTAB_MAX_BATCH)
+        return MTCP_GPU_EINVAL;
+    mtcp_gpu_ctx *ctx = tab->ctx;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n_del == 0 && n_ins == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    if (n_del)
+        hipLaunchKernelGGL(mg::flowtab_remove_kernel, flowtab_grid(ctx, n_del), dim3(mg::kBlock), 0, st, tab->slots,
+                           flowtab_mask(tab), reinterpret_cast<const uint4 *>(d_del), n_del, tab->stats);
+    if (n_ins)
+        hipLaunchKernelGGL(mg::flowtab_insert_kernel, flowtab_grid(ctx, n_ins), dim3(mg::kBlock), 0, st, tab->slots,
+                           flowtab_mask(tab), reinterpret_cast<const uint4 *>(d_ins), n_ins, tab->stats);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+int mtcp_gpu_flowtab_lookup_dev(mtcp_gpu_flowtab *tab, const mtcp_gpu_result *d_res, uint32_t n,
+                                uint32_t *d_sid, uint32_t *d_bins, void *stream) {
+    if (!tab || (n && (!d_res || !d_sid)) || ((uintptr_t)d_res & 7) || ((uintptr_t)d_sid & 3) ||
+        ((uintptr_t)d_bins & 3) || n > MTCP_GPU_FLOWTAB_MAX_BATCH ||
+        (tab->ctx->flags & MTCP_GPU_F_COMPACT))     // reads 40 B records (the 4-tuple)
+        return MTCP_GPU_EINVAL;
+    mtcp_gpu_ctx *ctx = tab->ctx;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    hipLaunchKernelGGL(mg::flowtab_lookup_kernel<kFlowtabGroup>, flowtab_grid(ctx, n), dim3(mg::kBlock), 0,
+                       pick(ctx, stream), d_res, n, tab->slots, flowtab_mask(tab), d_sid, d_bins);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+// Built like mtcp_gpu_flow_hash: the entries go up into stage 0's chunk
+// buffer (removes, then inserts), the kernels run behind them.
+int mtcp_gpu_flowtab_update(mtcp_gpu_flowtab *tab, const mtcp_gpu_flow_entry *del, uint32_t n_del,
+                            const mtcp_gpu_flow_entry *ins, uint32_t n_ins) {
+    if (!tab || (n_del && !del) || (n_ins && !ins) || n_del > MTCP_GPU_FLOWTAB_MAX_BATCH ||
+        n_ins > MTCP_GPU_FLOWTAB_MAX_BATCH || !flowtab_ids_ok(del, n_del) || !flowtab_ids_ok(ins, n_ins))
+        return MTCP_GPU_EINVAL;
+    mtcp_gpu_ctx *ctx = tab->ctx;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n_del == 0 && n_ins == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const bool bounce = dl.bounded;
+    const uint64_t dbytes = (uint64_t)n_del * 16, ibytes = (uint64_t)n_ins * 16;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, dbytes + ibytes, 0, dl);
+    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, dbytes + ibytes, 0, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    const mtcp_gpu_flow_entry *d_del = reinterpret_cast<const mtcp_gpu_flow_entry *>(s.d_buf);
+    const mtcp_gpu_flow_entry *d_ins = d_del + n_del;
+    if (bounce) {
+        if (dbytes) memcpy(s.h_in, del, dbytes);
+        if (ibytes) memcpy(s.h_in + dbytes, ins, ibytes);
+        if (!HIP_OK(hipMemcpyAsync(s.d_buf, s.h_in, dbytes + ibytes, hipMemcpyHostToDevice, s.stream)))
+            rc = MTCP_GPU_EIO;
+    } else {
+        if (dbytes && !HIP_OK(hipMemcpyAsync(s.d_buf, del, dbytes, hipMemcpyHostToDevice, s.stream)))
+            rc = MTCP_GPU_EIO;
+        if (ibytes && !HIP_OK(hipMemcpyAsync(s.d_buf + dbytes, ins, ibytes, hipMemcpyHostToDevice, s.stream)))
+            rc = MTCP_GPU_EIO;
+    }
+    if (rc == MTCP_GPU_OK)
+        rc = mtcp_gpu_flowtab_update_dev(tab, n_del ? d_del : nullptr, n_del, n_ins ? d_ins : nullptr, n_ins,
+                                         s.stream);
+    return finish_call(ctx, rc, dl, 1);
+}
+
+// The records go up into stage 0's record buffer; its chunk buffer holds
+// sid[n], then bins[n].
+int mtcp_gpu_flowtab_lookup(mtcp_gpu_flowtab *tab, const mtcp_gpu_result *res, uint32_t n, uint32_t *sid,
+                            uint32_t *bins) {
+    if (!tab || (n && (!res || !sid)) || n > MTCP_GPU_FLOWTAB_MAX_BATCH || (tab->ctx->flags & MTCP_GPU_F_COMPACT))
+        return MTCP_GPU_EINVAL;
+    mtcp_gpu_ctx *ctx = tab->ctx;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const bool bounce = dl.bounded;
+    const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_result), sbytes = (uint64_t)n * sizeof(uint32_t);
+    const uint64_t obytes = bins ? 2 * sbytes : sbytes;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, obytes, n, dl);
+    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, rbytes, obytes, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    const void *src = res;
+    if (bounce) {
+        memcpy(s.h_in, res, rbytes);
+        src = s.h_in;
+    }
+    uint32_t *d_sid = reinterpret_cast<uint32_t *>(s.d_buf);
+    uint32_t *d_bins = bins ? d_sid + n : nullptr;
+    if (!HIP_OK(hipMemcpyAsync(s.d_out, src, rbytes, hipMemcpyHostToDevice, s.stream))) rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK) rc = mtcp_gpu_flowtab_lookup_dev(tab, s.d_out, n, d_sid, d_bins, s.stream);
+    if (rc == MTCP_GPU_OK && bounce &&
+        !HIP_OK(hipMemcpyAsync(s.h_out, d_sid, obytes, hipMemcpyDeviceToHost, s.stream)))
+        rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK && !bounce &&
+        (!HIP_OK(hipMemcpyAsync(sid, d_sid, sbytes, hipMemcpyDeviceToHost, s.stream)) ||
+         (bins && !HIP_OK(hipMemcpyAsync(bins, d_bins, sbytes, hipMemcpyDeviceToHost, s.stream)))))
+        rc = MTCP_GPU_EIO;
+    rc = finish_call(ctx, rc, dl, 1);
+    if (rc == MTCP_GPU_OK && bounce) {
+        memcpy(sid, s.h_out, sbytes);
+        if (bins) memcpy(bins, s.h_out + sbytes, sbytes);
+    }
+    return rc;
+}
+
+int mtcp_gpu_flowtab_stats(mtcp_gpu_flowtab *tab, mtcp_gpu_flowtab_counters *stats) {
+    if (!tab || !stats) return MTCP_GPU_EINVAL;
+    mtcp_gpu_ctx *ctx = tab->ctx;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    int rc = HIP_OK(hipMemcpyAsync(tab->h_stats, tab->stats, 16, hipMemcpyDeviceToHost, ctx->stream))
+                 ? waited(ctx, drain(ctx->stream, dl)) : MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK) *stats = *tab->h_stats;
+    return rc;
+}
+
+int mtcp_gpu_flowtab_rehash(mtcp_gpu_flowtab *tab) {
+    if (!tab) return MTCP_GPU_EINVAL;
+    mtcp_gpu_ctx *ctx = tab->ctx;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    uint4 *fresh = nullptr;
+    if (!HIP_OK(mtcp_park::alloc(&fresh, flowtab_bytes(tab), mtcp_park::kDevice))) return MTCP_GPU_ENOMEM;
+    int rc = MTCP_GPU_OK;
+    // live and tombs (the first 8 B of the counters) start again from 0
+    if (!HIP_OK(hipMemsetAsync(fresh, 0xFF, flowtab_bytes(tab), ctx->stream)) ||
+        !HIP_OK(hipMemsetAsync(tab->stats, 0, 8, ctx->stream)))
+        rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK) {
+        hipLaunchKernelGGL(mg::flowtab_rehash_kernel, flowtab_grid(ctx, 1u << tab->cap_log2), dim3(mg::kBlock), 0,
+                           ctx->stream, tab->slots, fresh, flowtab_mask(tab), tab->stats);
+        if (!HIP_OK(hipGetLastError())) rc = MTCP_GPU_EIO;
+    }
+    rc = waited(ctx, rc == MTCP_GPU_OK ? drain(ctx->stream, dl) : rc);
+    if (rc == MTCP_GPU_ETIMEDOUT) return rc;     // both arrays stay: the launch may still run
+    if (rc == MTCP_GPU_OK) std::swap(fresh, tab->slots);
+    mtcp_park::release(fresh, flowtab_bytes(tab), mtcp_park::kDevice, !dl.bounded);
     return rc;
 }
 

@@ -151,8 +151,10 @@ __device__ __forceinline__ uint32_t row_bcast(uint32_t v, int i) {
 
 // Jenkins one-at-a-time over the 12 key bytes, each read as a signed char
 // (tcp_stream.c:77-87 `char *key`; x86 char is signed).  The bytes of w are
-// key bytes 4q..4q+3 in memory order.
-__device__ __forceinline__ uint32_t hash_flow(const uint32_t (&w)[3]) {
+// key bytes 4q..4q+3 in memory order.  hash_flow32 is the value before
+// HashFlow's mask (the device flow table's home slot comes from it, and the
+// host computes the same for mtcp_gpu_flowtab_home); hash_flow is HashFlow.
+__host__ __device__ __forceinline__ uint32_t hash_flow32(const uint32_t (&w)[3]) {
     uint32_t h = 0;
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
@@ -163,16 +165,28 @@ __device__ __forceinline__ uint32_t hash_flow(const uint32_t (&w)[3]) {
     h += h << 3;
     h ^= h >> 11;
     h += h << 15;
-    return h & (MTCP_GPU_NUM_BINS_FLOWS - 1);
+    return h;
 }
 
-// The flow-table bin of one rx record (f3): HashFlow of the key
-// ProcessTCPPacket hands to StreamHTSearch (tcp_in.c:1180-1186: saddr =
-// iph->daddr, daddr = iph->saddr, sport = tcph->dest, dport = tcph->source),
-// FLOW_NONE for packets that never get there.
+__device__ __forceinline__ uint32_t hash_flow(const uint32_t (&w)[3]) {
+    return hash_flow32(w) & (MTCP_GPU_NUM_BINS_FLOWS - 1);
+}
+
+// The stream key of one rx record, as ProcessTCPPacket hands it to
+// StreamHTSearch (tcp_in.c:1180-1186: saddr = iph->daddr, daddr = iph->saddr,
+// sport = tcph->dest, dport = tcph->source).
+__device__ __forceinline__ void flow_key(uint32_t saddr, uint32_t daddr, uint32_t ports, uint32_t (&w)[3]) {
+    w[0] = daddr;
+    w[1] = saddr;
+    w[2] = (ports >> 16) | (ports << 16);
+}
+
+// The flow-table bin of one rx record (f3): HashFlow of that key, FLOW_NONE
+// for packets that never get there.
 __device__ __forceinline__ uint32_t flow_bin(uint32_t saddr, uint32_t daddr, uint32_t ports,
                                              uint32_t verdict) {
-    const uint32_t w[3] = {daddr, saddr, (ports >> 16) | (ports << 16)};
+    uint32_t w[3];
+    flow_key(saddr, daddr, ports, w);
     return verdict == MTCP_GPU_V_TCP_OK ? hash_flow(w) : MTCP_GPU_FLOW_NONE;
 }
 

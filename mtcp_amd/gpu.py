@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from ._lib import check, lib
-from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
+from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
                      TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
@@ -429,6 +429,78 @@ class Context:
                                               max_out, ctypes.byref(found)),
               "mtcp_gpu_addr_pool_search")
         return out[:min(found.value, max_out)]
+
+
+class FlowTable:
+    """One mtcp_gpu_flowtab (include/mtcp_gpu_flowtab.h): the device mirror of
+    a tcp_flow_table (mtcp/src/fhash.c:16-121) bound to `ctx`.  Close it
+    before its context."""
+
+    def __init__(self, ctx: Context, cap_log2: int):
+        self._h = ctypes.c_void_p()
+        self.ctx = ctx
+        check(lib().mtcp_gpu_flowtab_create(ctx._h, cap_log2, ctypes.byref(self._h)), "mtcp_gpu_flowtab_create")
+
+    @staticmethod
+    def home(key12: bytes, cap_log2: int) -> int:
+        """mtcp_gpu_flowtab_home (host only, needs no GPU)."""
+        b = (ctypes.c_uint8 * 12).from_buffer_copy(key12)
+        return lib().mtcp_gpu_flowtab_home(ctypes.cast(b, ctypes.c_void_p), cap_log2)
+
+    @property
+    def capacity(self) -> int:
+        return lib().mtcp_gpu_flowtab_capacity(self._h)
+
+    def close(self) -> None:
+        if self._h:
+            lib().mtcp_gpu_flowtab_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def update_dev(self, dele, n_del: int, ins, n_ins: int, stream=None) -> None:
+        """dele / ins: n x 16 B (FLOW_ENTRY_DTYPE) on the device, or None with a
+        count of 0; removes run first."""
+        with self.ctx._ordered(stream) as st:
+            check(lib().mtcp_gpu_flowtab_update_dev(self._h, None if dele is None else _dptr(dele), n_del,
+                                                    None if ins is None else _dptr(ins), n_ins, st),
+                  "mtcp_gpu_flowtab_update_dev")
+
+    def lookup_dev(self, res, n: int, sid, bins=None, stream=None) -> None:
+        """res: n x 40 B rx records; sid: n x u32; bins: n x u32 or None."""
+        with self.ctx._ordered(stream) as st:
+            check(lib().mtcp_gpu_flowtab_lookup_dev(self._h, _dptr(res), n, _dptr(sid),
+                                                    None if bins is None else _dptr(bins), st),
+                  "mtcp_gpu_flowtab_lookup_dev")
+
+    def update(self, dele: np.ndarray | None = None, ins: np.ndarray | None = None) -> None:
+        """mtcp_gpu_flowtab_update: entries in host memory, removes first."""
+        dele = np.zeros(0, FLOW_ENTRY_DTYPE) if dele is None else np.ascontiguousarray(dele, dtype=FLOW_ENTRY_DTYPE)
+        ins = np.zeros(0, FLOW_ENTRY_DTYPE) if ins is None else np.ascontiguousarray(ins, dtype=FLOW_ENTRY_DTYPE)
+        check(lib().mtcp_gpu_flowtab_update(self._h, dele.ctypes.data if len(dele) else None, len(dele),
+                                            ins.ctypes.data if len(ins) else None, len(ins)),
+              "mtcp_gpu_flowtab_update")
+
+    def lookup(self, res: np.ndarray, bins: bool = False):
+        """mtcp_gpu_flowtab_lookup: sid, or (sid, bins), of 40 B records in host memory."""
+        res = np.ascontiguousarray(res, dtype=RESULT_DTYPE)
+        sid = np.zeros(len(res), dtype=np.uint32)
+        b = np.zeros(len(res), dtype=np.uint32) if bins else None
+        check(lib().mtcp_gpu_flowtab_lookup(self._h, res.ctypes.data, len(res), sid.ctypes.data,
+                                            b.ctypes.data if bins else None), "mtcp_gpu_flowtab_lookup")
+        return (sid, b) if bins else sid
+
+    def stats(self) -> dict:
+        c = np.zeros(1, dtype=FLOWTAB_COUNTERS_DTYPE)
+        check(lib().mtcp_gpu_flowtab_stats(self._h, c.ctypes.data), "mtcp_gpu_flowtab_stats")
+        return {f: int(c[f][0]) for f in FLOWTAB_COUNTERS_DTYPE.names}
+
+    def rehash(self) -> None:
+        check(lib().mtcp_gpu_flowtab_rehash(self._h), "mtcp_gpu_flowtab_rehash")
 
 
 def parse_cpulist(text: str) -> set[int]:
