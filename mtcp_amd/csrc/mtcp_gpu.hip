@@ -18,6 +18,7 @@
 
 #include "../../include/mtcp_gpu.h"
 #include "../../include/mtcp_gpu_flowtab.h"
+#include "../../include/mtcp_gpu_group.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
 #include "../../include/mtcp_gpu_txbuild.h"
@@ -26,6 +27,7 @@
 #include "dispatch.hpp"
 #include "flow_kernels.hpp"
 #include "flowtab_kernels.hpp"
+#include "group_kernels.hpp"
 #include "host_copy.hpp"
 #include "park.hpp"
 #include "rx_kernels.hpp"
@@ -1432,6 +1434,135 @@ int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, ui
         memcpy(start, s.h_out + ibytes, sbytes);
     }
     return rc;
+}
+
+// ---- grouping by stream --------------------------------------
+static_assert(MTCP_GPU_GROUP_MAX_PKTS == MTCP_GPU_FLOWTAB_MAX_BATCH, "a lookup's whole batch can be grouped");
+
+uint32_t mtcp_gpu_group_tile(void) { return mg::kGroupTile; }
+
+uint64_t mtcp_gpu_group_work_bytes(uint32_t n, uint32_t max_id) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return 0;
+    return mg::group_work(n, max_id).bytes;
+}
+
+int mtcp_gpu_group_dev(mtcp_gpu_ctx *ctx, const uint32_t *d_sid, uint32_t n, uint32_t max_id,
+                       uint32_t *d_idx, uint32_t *d_seg_sid, uint32_t *d_seg_start, uint32_t *d_nseg,
+                       void *d_work, uint64_t work_bytes, void *stream) {
+    if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
+        (n && (!d_sid || !d_idx || !d_seg_sid || !d_seg_start || !d_nseg || !d_work)) ||
+        ((uintptr_t)d_sid & 3) || ((uintptr_t)d_idx & 3) || ((uintptr_t)d_seg_sid & 3) ||
+        ((uintptr_t)d_seg_start & 3) || ((uintptr_t)d_nseg & 3) || ((uintptr_t)d_work & 15))
+        return MTCP_GPU_EINVAL;
+    const mg::GroupWork w = mg::group_work(n, max_id);
+    if (n && work_bytes < w.bytes) return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const dim3 block(mg::kBlock), tiles(w.ntiles);
+    if (w.one) {
+        hipLaunchKernelGGL(mg::group_one_kernel, dim3(1), block, 0, st, d_sid, n, max_id, d_idx, d_seg_sid,
+                           d_seg_start, d_nseg);
+        return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+    }
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    auto at = [&](uint64_t off) { return reinterpret_cast<uint32_t *>(work + off); };
+    uint32_t *cnt = at(w.cnt_off), *totals = at(w.tot_off), *segcnt = at(w.seg_off), *segtot = at(w.segtot_off);
+    // pass p reads the pairs pass p - 1 wrote (pass 0: d_sid, the index is the
+    // position) and writes keys to key[p & 1], indices to idx[p & 1] or d_idx
+    const uint32_t *src_key = d_sid, *src_idx = nullptr;
+    for (uint32_t p = 0; p < w.passes; ++p) {
+        const mg::GroupDigit d = mg::group_digit(w.key_bits, w.passes, p);
+        uint32_t *dst_key = at(w.key_off[p & 1]);
+        uint32_t *dst_idx = p + 1 == w.passes ? d_idx : at(w.idx_off[p & 1]);
+        if (p == 0)
+            hipLaunchKernelGGL(mg::group_count_kernel<true>, tiles, block, 0, st, src_key, n, max_id, d.shift, d.bits,
+                               cnt, w.ntiles);
+        else
+            hipLaunchKernelGGL(mg::group_count_kernel<false>, tiles, block, 0, st, src_key, n, max_id, d.shift,
+                               d.bits, cnt, w.ntiles);
+        hipLaunchKernelGGL(mg::group_scan_kernel, dim3(1u << d.bits), block, 0, st, reinterpret_cast<uint4 *>(cnt),
+                           w.ntiles, totals);
+        if (p == 0)
+            hipLaunchKernelGGL(mg::group_emit_kernel<true>, tiles, block, 0, st, src_key, src_idx, n, max_id, d.shift,
+                               d.bits, cnt, totals, w.ntiles, dst_key, dst_idx);
+        else
+            hipLaunchKernelGGL(mg::group_emit_kernel<false>, tiles, block, 0, st, src_key, src_idx, n, max_id,
+                               d.shift, d.bits, cnt, totals, w.ntiles, dst_key, dst_idx);
+        src_key = dst_key;
+        src_idx = dst_idx;
+    }
+    hipLaunchKernelGGL(mg::group_seg_count_kernel, tiles, block, 0, st, src_key, n, segcnt);
+    hipLaunchKernelGGL(mg::group_scan_kernel, dim3(1), block, 0, st, reinterpret_cast<uint4 *>(segcnt), w.ntiles,
+                       segtot);
+    hipLaunchKernelGGL(mg::group_seg_emit_kernel, tiles, block, 0, st, src_key, n, max_id, segcnt, segtot,
+                       d_seg_sid, d_seg_start, d_nseg);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+// Built like mtcp_gpu_steer.  Stage 0's chunk buffer holds sid[n], then the
+// outputs in one piece (nseg and 12 B of padding, idx[n], seg_sid[n],
+// seg_start[n + 1]), then the workspace.  m is known only on the device: a
+// bounded call brings the whole piece into its bounce buffer and copies out
+// what the contract names; an unbounded one fetches idx and nseg, waits, and
+// fetches the table's m and m + 1 entries.
+int mtcp_gpu_group(mtcp_gpu_ctx *ctx, const uint32_t *sid, uint32_t n, uint32_t max_id,
+                   uint32_t *idx, uint32_t *seg_sid, uint32_t *seg_start, uint32_t *nseg) {
+    if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
+        (n && (!sid || !idx || !seg_sid || !seg_start || !nseg)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const bool bounce = dl.bounded;
+    const uint64_t ibytes = (uint64_t)n * sizeof(uint32_t);
+    const uint64_t out_off = (ibytes + 15) & ~15ull;               // nseg, padded to 16 B
+    const uint64_t obytes = 16 + 3 * ibytes + sizeof(uint32_t);
+    const uint64_t work_off = (out_off + obytes + 15) & ~15ull;
+    const uint64_t wbytes = mg::group_work(n, max_id).bytes;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, work_off + wbytes, 0, dl);
+    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, ibytes, obytes, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    const void *src = sid;
+    if (bounce) {
+        memcpy(s.h_in, sid, ibytes);
+        src = s.h_in;
+    }
+    uint32_t *d_sid = reinterpret_cast<uint32_t *>(s.d_buf);
+    uint32_t *d_nseg = reinterpret_cast<uint32_t *>(s.d_buf + out_off);
+    uint32_t *d_idx = d_nseg + 4, *d_seg_sid = d_idx + n, *d_seg_start = d_seg_sid + n;
+    if (!HIP_OK(hipMemcpyAsync(d_sid, src, ibytes, hipMemcpyHostToDevice, s.stream))) rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK)
+        rc = mtcp_gpu_group_dev(ctx, d_sid, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, s.d_buf + work_off,
+                                wbytes, s.stream);
+    if (bounce) {
+        if (rc == MTCP_GPU_OK && !HIP_OK(hipMemcpyAsync(s.h_out, d_nseg, obytes, hipMemcpyDeviceToHost, s.stream)))
+            rc = MTCP_GPU_EIO;
+        rc = finish_call(ctx, rc, dl, 1);
+        if (rc == MTCP_GPU_OK) {
+            const uint32_t *h = reinterpret_cast<const uint32_t *>(s.h_out);
+            const uint32_t m = std::min(h[0], n);
+            nseg[0] = m;
+            memcpy(idx, h + 4, ibytes);
+            memcpy(seg_sid, h + 4 + n, (size_t)m * sizeof(uint32_t));
+            memcpy(seg_start, h + 4 + 2 * (size_t)n, ((size_t)m + 1) * sizeof(uint32_t));
+        }
+        return rc;
+    }
+    if (rc == MTCP_GPU_OK && (!HIP_OK(hipMemcpyAsync(idx, d_idx, ibytes, hipMemcpyDeviceToHost, s.stream)) ||
+                              !HIP_OK(hipMemcpyAsync(nseg, d_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream))))
+        rc = MTCP_GPU_EIO;
+    rc = finish_call(ctx, rc, dl, 1);
+    if (rc != MTCP_GPU_OK) return rc;
+    const uint32_t m = std::min(nseg[0], n);
+    if (!HIP_OK(hipMemcpyAsync(seg_sid, d_seg_sid, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream)) ||
+        !HIP_OK(hipMemcpyAsync(seg_start, d_seg_start, ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               s.stream)))
+        rc = MTCP_GPU_EIO;
+    return finish_call(ctx, rc, dl, 1);
 }
 
 // ---- device flow table ----------------------------------------

@@ -304,6 +304,37 @@ class Context:
                                    start.ctypes.data), "mtcp_gpu_steer")
         return idx, start
 
+    # -- grouping by stream (core.c:768-777, tcp_in.c:1181-1186; mtcp_gpu_group.h) --
+    @staticmethod
+    def group_tile() -> int:
+        return lib().mtcp_gpu_group_tile()
+
+    @staticmethod
+    def group_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_group_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_group_work_bytes(n, max_id)
+
+    def group_dev(self, sid, n: int, max_id: int, idx, seg_sid, seg_start, nseg, work, stream=None) -> None:
+        """sid: n x u32 as FlowTable.lookup_dev writes them; idx, seg_sid: n x u32;
+        seg_start: (n + 1) x u32; nseg: 1 x u32; work: at least
+        group_work_bytes(n, max_id) bytes, 16 B aligned."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_group_dev(self._h, _dptr(sid), n, max_id, _dptr(idx), _dptr(seg_sid),
+                                           _dptr(seg_start), _dptr(nseg), _dptr(work),
+                                           work.numel() * work.element_size(), st), "mtcp_gpu_group_dev")
+
+    def group(self, sid: np.ndarray, max_id: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """mtcp_gpu_group: (idx, seg_sid, seg_start) of stream ids in host memory,
+        the table cut to its m and m + 1 entries."""
+        sid = np.ascontiguousarray(sid, dtype=np.uint32)
+        n = len(sid)
+        idx, seg_sid = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        seg_start, nseg = np.zeros(n + 1, dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+        check(lib().mtcp_gpu_group(self._h, sid.ctypes.data, n, max_id, idx.ctypes.data, seg_sid.ctypes.data,
+                                   seg_start.ctypes.data, nseg.ctypes.data), "mtcp_gpu_group")
+        m = int(nseg[0])
+        return idx, seg_sid[:m], seg_start[:m + 1]
+
     # -- tx frames from segment records (tcp_out.c:135-354; mtcp_gpu_txbuild.h) --
     def tx_build_dev(self, seg, n: int, payload, links, buf, desc, off_shift: int, status,
                      max_mss: int = 0, flags: int = 0, stream=None) -> None:
