@@ -7,8 +7,6 @@
 // (mtcp/src/ip_in.c:29-31, tcp_in.c:1160-1164).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -28,6 +26,7 @@
 #include "flow_kernels.hpp"
 #include "flowtab_kernels.hpp"
 #include "group_kernels.hpp"
+#include "host_call.hpp"
 #include "host_copy.hpp"
 #include "park.hpp"
 #include "rx_kernels.hpp"
@@ -40,38 +39,7 @@
 
 namespace {
 
-constexpr int kStages = 3;                       // H2D | kernel | D2H overlap
-constexpr uint64_t kStageBytes = 64ull << 20;    // chunk bytes per pipeline stage
-constexpr uint32_t kStagePkts = 1u << 16;        // descriptors per pipeline stage
-
-// One pipeline stage of the host-memory calls.  Stage 0 runs on the
-// context's own stream (one stream per mTCP thread: an io_module's rxqs, its
-// tx fills and every host call of a batch that fits one stage share it);
-// stages 1 and 2 get streams of their own only when a call spans more than
-// one stage (a chunk above kStageBytes), to overlap H2D, kernel and D2H.
-struct Stage {
-    uint8_t *d_buf = nullptr;
-    mtcp_gpu_desc *d_desc = nullptr;
-    mtcp_gpu_result *d_out = nullptr;
-    uint64_t buf_cap = 0;
-    uint32_t pkt_cap = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // bounded calls (a context wait limit): pinned bounce buffers, so that
-    // no copy the call gives up on can read or write the caller's memory
-    uint8_t *h_in = nullptr;                    // caller data -> H2D
-    uint64_t h_in_cap = 0;
-    uint8_t *h_out = nullptr;                   // D2H -> caller data
-    uint64_t h_out_cap = 0;
-    uint32_t pend_first = 0, pend_cnt = 0;      // records of this stage's batch not yet copied out
-    // mtcp_gpu_rx_chunk_opts only: the batch's option records (kStagePkts of
-    // them, allocated by the first such call), their bounce buffer, and where
-    // a bounded call's pending ones go (set with pend_cnt; null: none)
-    mtcp_gpu_tcpopt *d_opt = nullptr;
-    mtcp_gpu_tcpopt *h_opt = nullptr;
-    mtcp_gpu_tcpopt *pend_opt = nullptr;
-};
-
+using namespace mtcp_host;   // Stage, HostCall and the staging constants (host_call.hpp)
 using mtcp_wait::Deadline;
 using mtcp_wait::drain;
 
@@ -101,36 +69,6 @@ struct mtcp_gpu_ctx {
 };
 
 namespace {
-
-// MTCP_GPU_DEBUG=1 in the environment: report every failing HIP call.
-bool hip_ok(hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    static const bool debug = getenv("MTCP_GPU_DEBUG") != nullptr;
-    if (debug) fprintf(stderr, "mtcp_gpu: %s -> %s\n", what, hipGetErrorString(e));
-    return false;
-}
-#define HIP_OK(x) hip_ok((x), #x)
-
-// Makes `device` current for one ABI call and restores the caller's device
-// on return: an mTCP thread (or a torch process) keeps the device it chose.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false, switched = false;
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev == device) {
-            ok = true;
-        } else {
-            ok = HIP_OK(hipSetDevice(device));
-            switched = ok && prev >= 0;
-        }
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
 
 // util/rss.c:13-105 (BuildKeyCache), then the 24 nibble tables the kernel
 // XORs: table[t][v] = XOR of cache[4t + m] over the bits of nibble v, MSB
@@ -427,56 +365,44 @@ int stage_host(mtcp_gpu_ctx *ctx, Stage &s, uint64_t in_bytes, uint64_t out_byte
     return MTCP_GPU_OK;
 }
 
-// A bounded call's copy of caller memory into a bounce buffer (16 B aligned
-// destination; streaming stores: the DMA engine reads it next, not a core)
-void bounce_in(uint8_t *dst, const void *src, uint64_t len) {
-    const uint8_t *p = static_cast<const uint8_t *>(src);
-    constexpr uint64_t kPiece = 1u << 30;
-    for (uint64_t o = 0; o < len; o += kPiece)
-        stage_copy(dst + o, p + o, (uint32_t)std::min(kPiece, len - o));
-    stage_fence();
-}
-
 // The end of a host call that used stages [0, nstages): every stage's
-// stream drained within the call's deadline, the records of a bounded
-// call's batches still in the stages' bounce buffers copied out to `out_b`
-// (rec bytes each).  Returns the call's result: rc if every drain
-// succeeded, MTCP_GPU_ETIMEDOUT (the context abandoned, nothing more copied
-// out) past the deadline.
-int finish_call(mtcp_gpu_ctx *ctx, int rc, const Deadline &dl, int nstages, uint8_t *out_b = nullptr,
-                size_t rec = 0) {
-    for (int i = 0; i < nstages; ++i) {
+// stream drained within the call's deadline, then what a bounded call's
+// batches still owe the caller copied out (only if the result is MTCP_GPU_OK).
+// Returns rc if every drain succeeded, MTCP_GPU_ETIMEDOUT (the context
+// abandoned) past the deadline — or at once, without a further wait, if a
+// wait of the call gave up before.
+int finish_call(mtcp_gpu_ctx *ctx, int rc, const Deadline &dl, int nstages) {
+    for (int i = 0; i < nstages && rc != MTCP_GPU_ETIMEDOUT; ++i) {
         Stage &s = ctx->stage[i];
         if (!s.stream) continue;
-        const int r = drain(s.stream, dl);
-        if (r == MTCP_GPU_ETIMEDOUT) {
-            for (auto &t : ctx->stage) t.pend_cnt = 0;
-            return waited(ctx, r);
-        }
-        if (r != MTCP_GPU_OK && rc == MTCP_GPU_OK) rc = r;
+        const int r = waited(ctx, drain(s.stream, dl));
+        if (r == MTCP_GPU_ETIMEDOUT || rc == MTCP_GPU_OK) rc = r;
     }
-    for (int i = 0; i < nstages; ++i) {
-        Stage &s = ctx->stage[i];
-        if (rc == MTCP_GPU_OK && s.pend_cnt && out_b) {
-            memcpy(out_b + (size_t)s.pend_first * rec, s.h_out, (size_t)s.pend_cnt * rec);
-            if (s.pend_opt) memcpy(s.pend_opt, s.h_opt, (size_t)s.pend_cnt * sizeof(mtcp_gpu_tcpopt));
-        }
-        s.pend_cnt = 0;
-    }
+    for (auto &s : ctx->stage) rc == MTCP_GPU_OK ? stage_copy_out(s) : stage_drop(s);
     return rc;
 }
 
 // A bounded call reuses stage s for its next batch: the batch it holds
 // finishes (within the deadline) and its records are copied out.
-int stage_collect(mtcp_gpu_ctx *ctx, Stage &s, uint8_t *out_b, size_t rec, const Deadline &dl) {
-    if (!s.pend_cnt) return MTCP_GPU_OK;
+int stage_collect(mtcp_gpu_ctx *ctx, Stage &s, const Deadline &dl) {
+    if (!s.npend) return MTCP_GPU_OK;
     const int rc = waited(ctx, drain(s.stream, dl));
-    if (rc != MTCP_GPU_OK) return rc;
-    memcpy(out_b + (size_t)s.pend_first * rec, s.h_out, (size_t)s.pend_cnt * rec);
-    if (s.pend_opt) memcpy(s.pend_opt, s.h_opt, (size_t)s.pend_cnt * sizeof(mtcp_gpu_tcpopt));
-    s.pend_cnt = 0;
-    return MTCP_GPU_OK;
+    if (rc == MTCP_GPU_OK) stage_copy_out(s);
+    return rc;
 }
+
+// host_call.hpp's backend: the copies of a call on stage 0 go on the
+// context's stream, and a round ends in finish_call.
+struct HipBackend {
+    mtcp_gpu_ctx *ctx;
+    const Deadline &dl;
+    bool copy(void *dst, const void *src, uint64_t bytes, bool up) {
+        return HIP_OK(hipMemcpyAsync(dst, src, bytes, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost,
+                                     ctx->stage[0].stream));
+    }
+    int drain(int rc) { return finish_call(ctx, rc, dl, 1); }
+};
+using Call = HostCall<HipBackend>;
 
 // The option records' staging of a stage (mtcp_gpu_rx_chunk_opts): allocated
 // once, at full stage size, so it never grows under a batch in flight.
@@ -873,22 +799,34 @@ namespace {
 // through kStages stages — stage 0 on the context's stream, 1 and 2 on their
 // own — so that the H2D of batch b+1 overlaps the kernel of b and the D2H of
 // b-1.  Each batch copies only the byte span its packets occupy and the
-// kernel rebases descriptor offsets by that span's start.  Unbounded (the
-// context has no wait limit): the copies read the caller's chunk and write
-// its records directly.  Bounded: every byte passes through the stages'
-// pinned bounce buffers (`owned`: buf / desc already are the context's own
-// pinned gather and are not copied again), so that no copy the call gives up
-// on at its deadline can touch the caller's memory afterwards.
-// mtcp_gpu_rx_chunk_opts: the option kernel behind a stage's rx launch, on the
-// stage's stream, over the same frames and the records rx just wrote, and the
-// batch's option records on their way out (dst: the caller's, for this batch).
-int opts_batch(mtcp_gpu_ctx *ctx, Stage &s, const mg::KParams &kp, mtcp_gpu_tcpopt *dst, bool bounce) {
-    int rc = stage_opts(s, bounce);
-    if (rc == MTCP_GPU_OK) rc = launch_tcpopt<false>(ctx, kp, s.d_out, s.d_opt, s.stream);
+// kernel rebases descriptor offsets by that span's start.  The contract of
+// host_call.hpp per stage: a bounded call bounces every byte through the
+// stage's pinned buffers (`owned`: buf / desc already are the context's own
+// pinned gather and are not copied again).
+//
+// One batch on stage s, its frames already on their way into s.d_buf: the
+// descriptors up, the rx launch, for mtcp_gpu_rx_chunk_opts the option kernel
+// over the same frames and the records rx just wrote, then the records (and
+// option records) down — to out (opts), or for a bounded call into the stage's
+// bounce buffers, owed to the caller once the stage has drained.
+int rx_batch(mtcp_gpu_ctx *ctx, Stage &s, mg::KParams kp, const void *dsrc,
+             const mtcp_gpu_size_hint &hint, uint8_t *out, mtcp_gpu_tcpopt *opts, bool bounce) {
+    const size_t rbytes = kp.n * (size_t)record_size(kp), obytes = (size_t)kp.n * sizeof(mtcp_gpu_tcpopt);
+    kp.desc = s.d_desc;
+    kp.out = s.d_out;
+    int rc = HIP_OK(hipMemcpyAsync(s.d_desc, dsrc, (size_t)kp.n * sizeof(mtcp_gpu_desc), hipMemcpyHostToDevice,
+                                   s.stream)) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK) rc = launch<mg::kRxChunk>(ctx, kp, s.stream, &hint);
+    if (rc == MTCP_GPU_OK && opts) rc = stage_opts(s, bounce);
+    if (rc == MTCP_GPU_OK && opts) rc = launch_tcpopt<false>(ctx, kp, s.d_out, s.d_opt, s.stream);
     if (rc == MTCP_GPU_OK &&
-        !HIP_OK(hipMemcpyAsync(bounce ? s.h_opt : dst, s.d_opt, (size_t)kp.n * sizeof(mtcp_gpu_tcpopt),
-                               hipMemcpyDeviceToHost, s.stream)))
+        ((opts && !HIP_OK(hipMemcpyAsync(bounce ? s.h_opt : opts, s.d_opt, obytes, hipMemcpyDeviceToHost, s.stream))) ||
+         !HIP_OK(hipMemcpyAsync(bounce ? s.h_out : out, s.d_out, rbytes, hipMemcpyDeviceToHost, s.stream))))
         rc = MTCP_GPU_EIO;
+    if (rc == MTCP_GPU_OK && bounce) {
+        stage_pend(s, out, s.h_out, rbytes);
+        if (opts) stage_pend(s, opts, s.h_opt, obytes);
+    }
     return rc;
 }
 
@@ -900,6 +838,8 @@ int rx_host(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len, const mtcp_
     const size_t rec = (size_t)record_size(ctx);
     const bool bounce = dl.bounded;
     const uint64_t out_bytes = (uint64_t)kStagePkts * rec;
+    mg::KParams kp = base_params(ctx);
+    kp.off_shift = off_shift;
     if (!offsets_sorted(desc, n)) {
         // arbitrary order: stage the whole chunk once, then batches of descriptors
         Stage &s = ctx->stage[0];
@@ -914,34 +854,15 @@ int rx_host(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len, const mtcp_
         }
         if (rc == MTCP_GPU_OK && !HIP_OK(hipMemcpyAsync(s.d_buf, src, buf_len, hipMemcpyHostToDevice, s.stream)))
             rc = MTCP_GPU_EIO;
+        kp.buf = s.d_buf;
+        kp.buf_len = buf_len;
         for (uint32_t first = 0; first < n && rc == MTCP_GPU_OK; first += kStagePkts) {
-            const uint32_t cnt = std::min(n - first, kStagePkts);
-            if ((rc = stage_collect(ctx, s, out_b, rec, dl)) != MTCP_GPU_OK) break;   // the previous batch
-            const mtcp_gpu_desc *dsrc = desc + first;
-            if (bounce && !owned) {
-                mtcp_gpu_desc *d = reinterpret_cast<mtcp_gpu_desc *>(s.h_in + padded);
-                memcpy(d, desc + first, (size_t)cnt * sizeof(mtcp_gpu_desc));
-                dsrc = d;
-            }
-            const mtcp_gpu_size_hint hint = size_hint(desc + first, cnt);
-            mg::KParams kp = base_params(ctx);
-            kp.buf = s.d_buf;
-            kp.buf_len = buf_len;
-            kp.desc = s.d_desc;
-            kp.n = cnt;
-            kp.off_shift = off_shift;
-            kp.out = s.d_out;
-            if (!HIP_OK(hipMemcpyAsync(s.d_desc, dsrc, (size_t)cnt * sizeof(mtcp_gpu_desc),
-                                       hipMemcpyHostToDevice, s.stream)))
-                rc = MTCP_GPU_EIO;
-            if (rc == MTCP_GPU_OK) rc = launch<mg::kRxChunk>(ctx, kp, s.stream, &hint);
-            if (rc == MTCP_GPU_OK && opts) rc = opts_batch(ctx, s, kp, opts + first, bounce);
-            if (rc == MTCP_GPU_OK &&
-                !HIP_OK(hipMemcpyAsync(bounce ? s.h_out : out_b + first * rec, s.d_out, cnt * rec,
-                                       hipMemcpyDeviceToHost, s.stream)))
-                rc = MTCP_GPU_EIO;
-            if (rc == MTCP_GPU_OK && bounce)
-                s.pend_first = first, s.pend_cnt = cnt, s.pend_opt = opts ? opts + first : nullptr;
+            kp.n = std::min(n - first, kStagePkts);
+            if ((rc = stage_collect(ctx, s, dl)) != MTCP_GPU_OK) break;   // the previous batch
+            const void *dsrc = desc + first;
+            if (bounce && !owned) dsrc = memcpy(s.h_in + padded, desc + first, (size_t)kp.n * sizeof(mtcp_gpu_desc));
+            rc = rx_batch(ctx, s, kp, dsrc, size_hint(desc + first, kp.n), out_b + first * rec,
+                          opts ? opts + first : nullptr, bounce);
         }
     } else {
         uint32_t first = 0;
@@ -964,49 +885,32 @@ int rx_host(mtcp_gpu_ctx *ctx, const uint8_t *buf, uint64_t buf_len, const mtcp_
             if (!hint.max_len) hint.min_len = 0;
             Stage &s = ctx->stage[b % kStages];
             const uint64_t span = hi - lo, padded = (span + 15) & ~15ull;
-            if ((rc = stage_collect(ctx, s, out_b, rec, dl)) != MTCP_GPU_OK) break;   // its batch b - kStages
+            if ((rc = stage_collect(ctx, s, dl)) != MTCP_GPU_OK) break;   // its batch b - kStages
             rc = stage_reserve(ctx, s, padded + 16, kStagePkts, dl);
             if (rc == MTCP_GPU_OK && bounce)
                 rc = stage_host(ctx, s, owned ? 0 : padded + (uint64_t)cnt * sizeof(mtcp_gpu_desc), out_bytes, dl);
             if (rc != MTCP_GPU_OK) break;
             const uint8_t *src = buf + lo;
-            const mtcp_gpu_desc *dsrc = desc + first;
+            const void *dsrc = desc + first;
             if (bounce && !owned) {
                 bounce_in(s.h_in, buf + lo, span);
-                memcpy(s.h_in + padded, desc + first, (size_t)cnt * sizeof(mtcp_gpu_desc));
                 src = s.h_in;
-                dsrc = reinterpret_cast<const mtcp_gpu_desc *>(s.h_in + padded);
+                dsrc = memcpy(s.h_in + padded, desc + first, (size_t)cnt * sizeof(mtcp_gpu_desc));
             }
-            mg::KParams kp = base_params(ctx);
             kp.buf = s.d_buf;
             kp.buf_len = span;           // descriptors are bounded by the caller's buf_len
             kp.base_sub = (int64_t)lo;
-            kp.desc = s.d_desc;
             kp.n = cnt;
-            kp.off_shift = off_shift;
-            kp.out = s.d_out;
-            if ((span && !HIP_OK(hipMemcpyAsync(s.d_buf, src, span, hipMemcpyHostToDevice, s.stream))) ||
-                !HIP_OK(hipMemcpyAsync(s.d_desc, dsrc, (size_t)cnt * sizeof(mtcp_gpu_desc),
-                                       hipMemcpyHostToDevice, s.stream)))
+            if (span && !HIP_OK(hipMemcpyAsync(s.d_buf, src, span, hipMemcpyHostToDevice, s.stream)))
                 rc = MTCP_GPU_EIO;
-            if (rc == MTCP_GPU_OK) rc = launch<mg::kRxChunk>(ctx, kp, s.stream, &hint);
-            if (rc == MTCP_GPU_OK && opts) rc = opts_batch(ctx, s, kp, opts + first, bounce);
-            if (rc == MTCP_GPU_OK &&
-                !HIP_OK(hipMemcpyAsync(bounce ? s.h_out : out_b + first * rec, s.d_out, cnt * rec,
-                                       hipMemcpyDeviceToHost, s.stream)))
-                rc = MTCP_GPU_EIO;
-            if (rc == MTCP_GPU_OK && bounce)
-                s.pend_first = first, s.pend_cnt = cnt, s.pend_opt = opts ? opts + first : nullptr;
+            if (rc == MTCP_GPU_OK)
+                rc = rx_batch(ctx, s, kp, dsrc, hint, out_b + first * rec, opts ? opts + first : nullptr, bounce);
             first += cnt;
         }
     }
-    // a stage_collect that timed out has abandoned the context already: no
-    // more waits, and no stage's records are copied out
-    if (rc == MTCP_GPU_ETIMEDOUT) {
-        for (auto &t : ctx->stage) t.pend_cnt = 0;
-        return rc;
-    }
-    return finish_call(ctx, rc, dl, kStages, out_b, rec);
+    // (a stage_collect that timed out has abandoned the context already: no
+    // more waits then, and no stage's records are copied out)
+    return finish_call(ctx, rc, dl, kStages);
 }
 
 // Gather a pointer burst into the context's pinned PSIO-style chunk (64 B
@@ -1046,6 +950,19 @@ int gather_burst(mtcp_gpu_ctx *ctx, const uint8_t *const *pkts, const uint16_t *
     stage_fence();
     *total_out = total;
     return MTCP_GPU_OK;
+}
+
+// The tx fill of the host calls: over the n frames staged in s.d_buf by the
+// descriptors in s.d_desc, reporting {checks, T} per frame into s.d_out.
+int launch_tx_report(mtcp_gpu_ctx *ctx, Stage &s, uint64_t buf_len, uint32_t n, uint32_t off_shift) {
+    mg::KParams kp = base_params(ctx);
+    kp.buf = s.d_buf;
+    kp.buf_len = buf_len;
+    kp.desc = s.d_desc;
+    kp.n = n;
+    kp.off_shift = off_shift;
+    kp.tx_report = reinterpret_cast<uint2 *>(s.d_out);                // n x 8 B <= n x 40 B
+    return launch<mg::kTxChunk>(ctx, kp, s.stream);
 }
 
 // The two check fields of a filled frame (the tx kernels' report: {ip check
@@ -1098,12 +1015,10 @@ int mtcp_gpu_rx_ptrs(mtcp_gpu_ctx *ctx, const uint8_t *const *pkts, const uint16
 // the frames are gathered into pinned staging and checked on the GPU, which
 // reports {checks, T} per frame (the tx kernels' report mode); only the two
 // check fields are written back into the caller's frames, here on the host,
-// once the report is in.  With a limit (timeout_us, else the context's wait
-// limit) the wait polls the device: past the limit nothing has been written
-// into the caller's frames, the call answers MTCP_GPU_ETIMEDOUT and the
-// context is abandoned (the copies may still run into its staging).  mTCP's
-// own tx fill never waits on a device (tcp_out.c:320-329, ip_out.c:147-165,
-// run from RunMainLoop core.c:818-824): the caller fills the frames itself.
+// once the report is in (within timeout_us, else the context's wait limit;
+// past it nothing has been written into the caller's frames).  mTCP's own tx
+// fill never waits on a device (tcp_out.c:320-329, ip_out.c:147-165, run from
+// RunMainLoop core.c:818-824): the caller fills the frames itself.
 int mtcp_gpu_tx_fill_ptrs_for(mtcp_gpu_ctx *ctx, uint8_t *const *pkts, const uint16_t *lens, uint32_t n,
                               uint32_t *n_filled, uint32_t timeout_us) {
     if (!ctx || (n && (!pkts || !lens))) return MTCP_GPU_EINVAL;
@@ -1120,25 +1035,14 @@ int mtcp_gpu_tx_fill_ptrs_for(mtcp_gpu_ctx *ctx, uint8_t *const *pkts, const uin
     if (rc != MTCP_GPU_OK) return rc;
     uint2 *report = reinterpret_cast<uint2 *>(ctx->h_gather_desc);    // reused once the H2D is done
     static_assert(sizeof(uint2) == sizeof(mtcp_gpu_desc), "report reuses the descriptor staging");
-    if (!HIP_OK(hipMemcpyAsync(s.d_buf, ctx->h_gather, total, hipMemcpyHostToDevice, s.stream)) ||
-        !HIP_OK(hipMemcpyAsync(s.d_desc, ctx->h_gather_desc, (size_t)n * sizeof(mtcp_gpu_desc),
-                               hipMemcpyHostToDevice, s.stream)))
-        rc = MTCP_GPU_EIO;
-    mg::KParams kp = base_params(ctx);
-    kp.buf = s.d_buf;
-    kp.buf_len = total;
-    kp.desc = s.d_desc;
-    kp.n = n;
-    kp.off_shift = 6;
-    kp.tx_report = reinterpret_cast<uint2 *>(s.d_out);                // n x 8 B <= n x 40 B
-    if (rc == MTCP_GPU_OK) rc = launch<mg::kTxChunk>(ctx, kp, s.stream);
-    if (rc == MTCP_GPU_OK && !HIP_OK(hipMemcpyAsync(report, s.d_out, (size_t)n * sizeof(uint2),
-                                                    hipMemcpyDeviceToHost, s.stream)))
-        rc = MTCP_GPU_EIO;
-    // every path drains the stream within the deadline, a failed enqueue's
-    // too: an H2D already queued may be reading the staging
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc != MTCP_GPU_OK) return rc;
+    // both ends of every copy are the context's own: the pinned gather up,
+    // the report down into the descriptors' place
+    Call hc(s, dl, {ctx, dl});
+    hc.h2d(s.d_buf, ctx->h_gather, total);
+    hc.h2d(s.d_desc, ctx->h_gather_desc, (size_t)n * sizeof(mtcp_gpu_desc));
+    if (hc.ok()) hc.note(launch_tx_report(ctx, s, total, n, 6));
+    hc.d2h(report, s.d_out, (size_t)n * sizeof(uint2));
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
     uint32_t cnt = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (!report[i].y) continue;
@@ -1157,10 +1061,8 @@ int mtcp_gpu_tx_fill_ptrs(mtcp_gpu_ctx *ctx, uint8_t *const *pkts, const uint16_
 // tx fill of a host chunk, in place: the chunk goes to the GPU once, the
 // kernel reports {checks, T} per frame (n x 8 B back instead of the whole
 // chunk) and the calling thread writes the two check fields of each filled
-// frame.  Bounded (a context wait limit): the chunk and the descriptors are
-// copied into pinned bounce buffers first, so that no copy given up on at
-// the deadline reads the caller's memory later, and nothing is written into
-// the chunk unless the report came in time.
+// frame.  Stages the chunk and the descriptors; the report comes down pinned,
+// and nothing is written into the chunk unless it came in time.
 int mtcp_gpu_tx_fill(mtcp_gpu_ctx *ctx, uint8_t *buf, uint64_t buf_len, const mtcp_gpu_desc *desc,
                      uint32_t n, uint32_t off_shift, uint32_t *n_filled) {
     if (!ctx || (n && (!buf || !desc)) || off_shift > 16) return MTCP_GPU_EINVAL;
@@ -1169,41 +1071,22 @@ int mtcp_gpu_tx_fill(mtcp_gpu_ctx *ctx, uint8_t *buf, uint64_t buf_len, const mt
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     Stage &s = ctx->stage[0];
     const uint64_t padded = (buf_len + 15) & ~15ull;
     const uint64_t dbytes = (uint64_t)n * sizeof(mtcp_gpu_desc);
     int rc = stage_reserve(ctx, s, padded + 16, n, dl);
-    if (rc == MTCP_GPU_OK) rc = stage_host(ctx, s, bounce ? padded + dbytes : 0, (uint64_t)n * sizeof(uint2), dl);
+    if (rc == MTCP_GPU_OK)
+        rc = stage_host(ctx, s, dl.bounded ? padded + dbytes : 0, (uint64_t)n * sizeof(uint2), dl);
     if (rc != MTCP_GPU_OK) return rc;
-    const uint8_t *src = buf;
-    const mtcp_gpu_desc *dsrc = desc;
-    if (bounce) {
-        bounce_in(s.h_in, buf, buf_len);
-        memcpy(s.h_in + padded, desc, dbytes);
-        src = s.h_in;
-        dsrc = reinterpret_cast<const mtcp_gpu_desc *>(s.h_in + padded);
-    }
+    Call hc(s, dl, {ctx, dl});
     // the 16 B past the chunk (the kernels' last vector load of a frame
     // ending there) read as zeros
-    if (!HIP_OK(hipMemsetAsync(s.d_buf + (buf_len & ~15ull), 0, 16, s.stream)) ||
-        !HIP_OK(hipMemcpyAsync(s.d_buf, src, buf_len, hipMemcpyHostToDevice, s.stream)) ||
-        !HIP_OK(hipMemcpyAsync(s.d_desc, dsrc, dbytes, hipMemcpyHostToDevice, s.stream)))
-        rc = MTCP_GPU_EIO;
-    mg::KParams kp = base_params(ctx);
-    kp.buf = s.d_buf;
-    kp.buf_len = buf_len;   // descriptor bound: the caller's length
-    kp.desc = s.d_desc;
-    kp.n = n;
-    kp.off_shift = off_shift;
-    kp.tx_report = reinterpret_cast<uint2 *>(s.d_out);                // n x 8 B <= n x 40 B
-    uint2 *report = reinterpret_cast<uint2 *>(s.h_out);
-    if (rc == MTCP_GPU_OK) rc = launch<mg::kTxChunk>(ctx, kp, s.stream);
-    if (rc == MTCP_GPU_OK && !HIP_OK(hipMemcpyAsync(report, s.d_out, (size_t)n * sizeof(uint2),
-                                                    hipMemcpyDeviceToHost, s.stream)))
-        rc = MTCP_GPU_EIO;
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc != MTCP_GPU_OK) return rc;
+    if (!HIP_OK(hipMemsetAsync(s.d_buf + (buf_len & ~15ull), 0, 16, s.stream))) hc.note(MTCP_GPU_EIO);
+    hc.up(s.d_buf, buf, buf_len, true);
+    hc.up(s.d_desc, desc, dbytes);
+    if (hc.ok()) hc.note(launch_tx_report(ctx, s, buf_len, n, off_shift));   // descriptor bound: the caller's length
+    const uint2 *report = reinterpret_cast<const uint2 *>(hc.down_pinned(s.d_out, (uint64_t)n * sizeof(uint2)));
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
     uint32_t cnt = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t off = (uint64_t)desc[i].offset << off_shift;
@@ -1268,6 +1151,7 @@ int mtcp_gpu_flow_hash_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, uint
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
+// The records go up into stage 0's record buffer; its chunk buffer holds bins[n].
 int mtcp_gpu_flow_hash(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n,
                        uint32_t *bins) {
     if (!ctx || (n && (!res || !bins)) || (ctx->flags & MTCP_GPU_F_COMPACT)) return MTCP_GPU_EINVAL;
@@ -1275,27 +1159,17 @@ int mtcp_gpu_flow_hash(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_result), bbytes = (uint64_t)n * sizeof(uint32_t);
     Stage &s = ctx->stage[0];
     int rc = stage_reserve(ctx, s, bbytes, n, dl);
-    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, rbytes, bbytes, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, rbytes, bbytes, dl);
     if (rc != MTCP_GPU_OK) return rc;
-    const void *src = res;
-    if (bounce) {
-        memcpy(s.h_in, res, rbytes);
-        src = s.h_in;
-    }
     uint32_t *d_bins = reinterpret_cast<uint32_t *>(s.d_buf);
-    if (!HIP_OK(hipMemcpyAsync(s.d_out, src, rbytes, hipMemcpyHostToDevice, s.stream)))
-        rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK) rc = mtcp_gpu_flow_hash_dev(ctx, s.d_out, n, d_bins, s.stream);
-    if (rc == MTCP_GPU_OK && !HIP_OK(hipMemcpyAsync(bounce ? (void *)s.h_out : (void *)bins, d_bins, bbytes,
-                                                    hipMemcpyDeviceToHost, s.stream)))
-        rc = MTCP_GPU_EIO;
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc == MTCP_GPU_OK && bounce) memcpy(bins, s.h_out, bbytes);
-    return rc;
+    Call hc(s, dl, {ctx, dl});
+    hc.up(s.d_out, res, rbytes);
+    if (hc.ok()) hc.note(mtcp_gpu_flow_hash_dev(ctx, s.d_out, n, d_bins, s.stream));
+    hc.down(bins, d_bins, bbytes);
+    return hc.finish();
 }
 
 // ---- steering by RSS queue ----------------------------------
@@ -1388,8 +1262,8 @@ int mtcp_gpu_steer_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, uint32_t
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Built like mtcp_gpu_flow_hash: the records go up into stage 0's record
-// buffer; its chunk buffer holds idx[n], start[Q + 2] and the workspace.
+// The records go up into stage 0's record buffer; its chunk buffer holds
+// idx[n], start[Q + 2] (adjacent: they come down together) and the workspace.
 int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, uint32_t flags,
                    uint32_t *idx, uint32_t *start) {
     if (!ctx || (flags & ~MTCP_GPU_STEER_DROP_BAD) || n > MTCP_GPU_STEER_MAX_PKTS ||
@@ -1399,7 +1273,6 @@ int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, ui
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     const uint32_t Q = steer_queues(ctx);
     const uint64_t rbytes = (uint64_t)n * record_size(ctx), ibytes = (uint64_t)n * sizeof(uint32_t);
     const uint64_t sbytes = ((uint64_t)Q + 2) * sizeof(uint32_t);
@@ -1407,33 +1280,17 @@ int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, ui
     const uint64_t wbytes = steer_work(Q, n).bytes;
     Stage &s = ctx->stage[0];
     int rc = stage_reserve(ctx, s, work_off + wbytes, n, dl);
-    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, rbytes, ibytes + sbytes, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, rbytes, ibytes + sbytes, dl);
     if (rc != MTCP_GPU_OK) return rc;
-    const void *src = res;
-    if (bounce) {
-        memcpy(s.h_in, res, rbytes);
-        src = s.h_in;
-    }
     uint32_t *d_idx = reinterpret_cast<uint32_t *>(s.d_buf);
     uint32_t *d_start = d_idx + n;
-    if (!HIP_OK(hipMemcpyAsync(s.d_out, src, rbytes, hipMemcpyHostToDevice, s.stream)))
-        rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK)
-        rc = mtcp_gpu_steer_dev(ctx, s.d_out, n, flags, d_idx, d_start, nullptr, nullptr, s.d_buf + work_off,
-                                wbytes, s.stream);
-    if (rc == MTCP_GPU_OK && bounce &&
-        !HIP_OK(hipMemcpyAsync(s.h_out, d_idx, ibytes + sbytes, hipMemcpyDeviceToHost, s.stream)))
-        rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK && !bounce &&
-        (!HIP_OK(hipMemcpyAsync(idx, d_idx, ibytes, hipMemcpyDeviceToHost, s.stream)) ||
-         !HIP_OK(hipMemcpyAsync(start, d_start, sbytes, hipMemcpyDeviceToHost, s.stream))))
-        rc = MTCP_GPU_EIO;
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc == MTCP_GPU_OK && bounce) {
-        memcpy(idx, s.h_out, ibytes);
-        memcpy(start, s.h_out + ibytes, sbytes);
-    }
-    return rc;
+    Call hc(s, dl, {ctx, dl});
+    hc.up(s.d_out, res, rbytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_steer_dev(ctx, s.d_out, n, flags, d_idx, d_start, nullptr, nullptr, s.d_buf + work_off,
+                                   wbytes, s.stream));
+    hc.down2(idx, d_idx, ibytes, start, sbytes);
+    return hc.finish();
 }
 
 // ---- grouping by stream --------------------------------------
@@ -1501,12 +1358,11 @@ int mtcp_gpu_group_dev(mtcp_gpu_ctx *ctx, const uint32_t *d_sid, uint32_t n, uin
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Built like mtcp_gpu_steer.  Stage 0's chunk buffer holds sid[n], then the
-// outputs in one piece (nseg and 12 B of padding, idx[n], seg_sid[n],
-// seg_start[n + 1]), then the workspace.  m is known only on the device: a
-// bounded call brings the whole piece into its bounce buffer and copies out
-// what the contract names; an unbounded one fetches idx and nseg, waits, and
-// fetches the table's m and m + 1 entries.
+// Stage 0's chunk buffer holds sid[n], then the outputs in one piece (nseg and
+// 12 B of padding, idx[n], seg_sid[n], seg_start[n + 1]), then the workspace.
+// m is known only on the device: a bounded call brings the whole piece down
+// pinned and copies out what the contract names; an unbounded one fetches idx
+// and nseg, waits, and fetches the table's m and m + 1 entries.
 int mtcp_gpu_group(mtcp_gpu_ctx *ctx, const uint32_t *sid, uint32_t n, uint32_t max_id,
                    uint32_t *idx, uint32_t *seg_sid, uint32_t *seg_start, uint32_t *nseg) {
     if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
@@ -1516,7 +1372,6 @@ int mtcp_gpu_group(mtcp_gpu_ctx *ctx, const uint32_t *sid, uint32_t n, uint32_t 
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     const uint64_t ibytes = (uint64_t)n * sizeof(uint32_t);
     const uint64_t out_off = (ibytes + 15) & ~15ull;               // nseg, padded to 16 B
     const uint64_t obytes = 16 + 3 * ibytes + sizeof(uint32_t);
@@ -1524,45 +1379,34 @@ int mtcp_gpu_group(mtcp_gpu_ctx *ctx, const uint32_t *sid, uint32_t n, uint32_t 
     const uint64_t wbytes = mg::group_work(n, max_id).bytes;
     Stage &s = ctx->stage[0];
     int rc = stage_reserve(ctx, s, work_off + wbytes, 0, dl);
-    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, ibytes, obytes, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, ibytes, obytes, dl);
     if (rc != MTCP_GPU_OK) return rc;
-    const void *src = sid;
-    if (bounce) {
-        memcpy(s.h_in, sid, ibytes);
-        src = s.h_in;
-    }
     uint32_t *d_sid = reinterpret_cast<uint32_t *>(s.d_buf);
     uint32_t *d_nseg = reinterpret_cast<uint32_t *>(s.d_buf + out_off);
     uint32_t *d_idx = d_nseg + 4, *d_seg_sid = d_idx + n, *d_seg_start = d_seg_sid + n;
-    if (!HIP_OK(hipMemcpyAsync(d_sid, src, ibytes, hipMemcpyHostToDevice, s.stream))) rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK)
-        rc = mtcp_gpu_group_dev(ctx, d_sid, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, s.d_buf + work_off,
-                                wbytes, s.stream);
-    if (bounce) {
-        if (rc == MTCP_GPU_OK && !HIP_OK(hipMemcpyAsync(s.h_out, d_nseg, obytes, hipMemcpyDeviceToHost, s.stream)))
-            rc = MTCP_GPU_EIO;
-        rc = finish_call(ctx, rc, dl, 1);
-        if (rc == MTCP_GPU_OK) {
-            const uint32_t *h = reinterpret_cast<const uint32_t *>(s.h_out);
-            const uint32_t m = std::min(h[0], n);
-            nseg[0] = m;
-            memcpy(idx, h + 4, ibytes);
-            memcpy(seg_sid, h + 4 + n, (size_t)m * sizeof(uint32_t));
-            memcpy(seg_start, h + 4 + 2 * (size_t)n, ((size_t)m + 1) * sizeof(uint32_t));
-        }
+    Call hc(s, dl, {ctx, dl});
+    hc.up(d_sid, sid, ibytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_group_dev(ctx, d_sid, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, s.d_buf + work_off,
+                                   wbytes, s.stream));
+    if (hc.bounded()) {
+        // one wait: nothing has reached the caller when it gives up
+        const uint32_t *h = reinterpret_cast<const uint32_t *>(hc.down_pinned(d_nseg, obytes));
+        if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+        const uint32_t m = std::min(h[0], n);
+        nseg[0] = m;
+        memcpy(idx, h + 4, ibytes);
+        memcpy(seg_sid, h + 4 + n, (size_t)m * sizeof(uint32_t));
+        memcpy(seg_start, h + 4 + 2 * (size_t)n, ((size_t)m + 1) * sizeof(uint32_t));
         return rc;
     }
-    if (rc == MTCP_GPU_OK && (!HIP_OK(hipMemcpyAsync(idx, d_idx, ibytes, hipMemcpyDeviceToHost, s.stream)) ||
-                              !HIP_OK(hipMemcpyAsync(nseg, d_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream))))
-        rc = MTCP_GPU_EIO;
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc != MTCP_GPU_OK) return rc;
+    hc.down(idx, d_idx, ibytes);
+    hc.down(nseg, d_nseg, sizeof(uint32_t));
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
     const uint32_t m = std::min(nseg[0], n);
-    if (!HIP_OK(hipMemcpyAsync(seg_sid, d_seg_sid, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream)) ||
-        !HIP_OK(hipMemcpyAsync(seg_start, d_seg_start, ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                               s.stream)))
-        rc = MTCP_GPU_EIO;
-    return finish_call(ctx, rc, dl, 1);
+    hc.down(seg_sid, d_seg_sid, (size_t)m * sizeof(uint32_t));
+    hc.down(seg_start, d_seg_start, ((size_t)m + 1) * sizeof(uint32_t));
+    return hc.finish();
 }
 
 // ---- device flow table ----------------------------------------
@@ -1697,8 +1541,8 @@ int mtcp_gpu_flowtab_lookup_dev(mtcp_gpu_flowtab *tab, const mtcp_gpu_result *d_
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Built like mtcp_gpu_flow_hash: the entries go up into stage 0's chunk
-// buffer (removes, then inserts), the kernels run behind them.
+// The entries go up into stage 0's chunk buffer (removes, then inserts,
+// adjacent: they go up together), the kernels run behind them.
 int mtcp_gpu_flowtab_update(mtcp_gpu_flowtab *tab, const mtcp_gpu_flow_entry *del, uint32_t n_del,
                             const mtcp_gpu_flow_entry *ins, uint32_t n_ins) {
     if (!tab || (n_del && !del) || (n_ins && !ins) || n_del > MTCP_GPU_FLOWTAB_MAX_BATCH ||
@@ -1709,33 +1553,23 @@ int mtcp_gpu_flowtab_update(mtcp_gpu_flowtab *tab, const mtcp_gpu_flow_entry *de
     if (n_del == 0 && n_ins == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     const uint64_t dbytes = (uint64_t)n_del * 16, ibytes = (uint64_t)n_ins * 16;
     Stage &s = ctx->stage[0];
     int rc = stage_reserve(ctx, s, dbytes + ibytes, 0, dl);
-    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, dbytes + ibytes, 0, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, dbytes + ibytes, 0, dl);
     if (rc != MTCP_GPU_OK) return rc;
     const mtcp_gpu_flow_entry *d_del = reinterpret_cast<const mtcp_gpu_flow_entry *>(s.d_buf);
     const mtcp_gpu_flow_entry *d_ins = d_del + n_del;
-    if (bounce) {
-        if (dbytes) memcpy(s.h_in, del, dbytes);
-        if (ibytes) memcpy(s.h_in + dbytes, ins, ibytes);
-        if (!HIP_OK(hipMemcpyAsync(s.d_buf, s.h_in, dbytes + ibytes, hipMemcpyHostToDevice, s.stream)))
-            rc = MTCP_GPU_EIO;
-    } else {
-        if (dbytes && !HIP_OK(hipMemcpyAsync(s.d_buf, del, dbytes, hipMemcpyHostToDevice, s.stream)))
-            rc = MTCP_GPU_EIO;
-        if (ibytes && !HIP_OK(hipMemcpyAsync(s.d_buf + dbytes, ins, ibytes, hipMemcpyHostToDevice, s.stream)))
-            rc = MTCP_GPU_EIO;
-    }
-    if (rc == MTCP_GPU_OK)
-        rc = mtcp_gpu_flowtab_update_dev(tab, n_del ? d_del : nullptr, n_del, n_ins ? d_ins : nullptr, n_ins,
-                                         s.stream);
-    return finish_call(ctx, rc, dl, 1);
+    Call hc(s, dl, {ctx, dl});
+    hc.up2(s.d_buf, del, dbytes, ins, ibytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_flowtab_update_dev(tab, n_del ? d_del : nullptr, n_del, n_ins ? d_ins : nullptr, n_ins,
+                                            s.stream));
+    return hc.finish();
 }
 
 // The records go up into stage 0's record buffer; its chunk buffer holds
-// sid[n], then bins[n].
+// sid[n], then bins[n] (adjacent: they come down together).
 int mtcp_gpu_flowtab_lookup(mtcp_gpu_flowtab *tab, const mtcp_gpu_result *res, uint32_t n, uint32_t *sid,
                             uint32_t *bins) {
     if (!tab || (n && (!res || !sid)) || n > MTCP_GPU_FLOWTAB_MAX_BATCH || (tab->ctx->flags & MTCP_GPU_F_COMPACT))
@@ -1745,35 +1579,19 @@ int mtcp_gpu_flowtab_lookup(mtcp_gpu_flowtab *tab, const mtcp_gpu_result *res, u
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_result), sbytes = (uint64_t)n * sizeof(uint32_t);
     const uint64_t obytes = bins ? 2 * sbytes : sbytes;
     Stage &s = ctx->stage[0];
     int rc = stage_reserve(ctx, s, obytes, n, dl);
-    if (rc == MTCP_GPU_OK && bounce) rc = stage_host(ctx, s, rbytes, obytes, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, rbytes, obytes, dl);
     if (rc != MTCP_GPU_OK) return rc;
-    const void *src = res;
-    if (bounce) {
-        memcpy(s.h_in, res, rbytes);
-        src = s.h_in;
-    }
     uint32_t *d_sid = reinterpret_cast<uint32_t *>(s.d_buf);
     uint32_t *d_bins = bins ? d_sid + n : nullptr;
-    if (!HIP_OK(hipMemcpyAsync(s.d_out, src, rbytes, hipMemcpyHostToDevice, s.stream))) rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK) rc = mtcp_gpu_flowtab_lookup_dev(tab, s.d_out, n, d_sid, d_bins, s.stream);
-    if (rc == MTCP_GPU_OK && bounce &&
-        !HIP_OK(hipMemcpyAsync(s.h_out, d_sid, obytes, hipMemcpyDeviceToHost, s.stream)))
-        rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK && !bounce &&
-        (!HIP_OK(hipMemcpyAsync(sid, d_sid, sbytes, hipMemcpyDeviceToHost, s.stream)) ||
-         (bins && !HIP_OK(hipMemcpyAsync(bins, d_bins, sbytes, hipMemcpyDeviceToHost, s.stream)))))
-        rc = MTCP_GPU_EIO;
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc == MTCP_GPU_OK && bounce) {
-        memcpy(sid, s.h_out, sbytes);
-        if (bins) memcpy(bins, s.h_out + sbytes, sbytes);
-    }
-    return rc;
+    Call hc(s, dl, {ctx, dl});
+    hc.up(s.d_out, res, rbytes);
+    if (hc.ok()) hc.note(mtcp_gpu_flowtab_lookup_dev(tab, s.d_out, n, d_sid, d_bins, s.stream));
+    hc.down2(sid, d_sid, sbytes, bins, bins ? sbytes : 0);
+    return hc.finish();
 }
 
 int mtcp_gpu_flowtab_stats(mtcp_gpu_flowtab *tab, mtcp_gpu_flowtab_counters *stats) {
@@ -1829,6 +1647,21 @@ bool txbuild_args_ok(const mtcp_gpu_ctx *ctx, uint32_t n, const void *seg, const
     const uintptr_t p0 = (uintptr_t)payload, b0 = (uintptr_t)buf;
     if (n && payload_bytes && buf_len && p0 < b0 + buf_len && b0 < p0 + payload_bytes) return false;
     return true;
+}
+
+// The built frames' bytes from the image in pinned staging into the caller's
+// buf; returns their number.
+static uint32_t copy_built(void *buf, const uint8_t *image, uint64_t buf_len, const mtcp_gpu_desc *desc,
+                    const uint8_t *status, uint32_t n, uint32_t off_shift) {
+    uint32_t cnt = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t off = (uint64_t)desc[i].offset << off_shift;
+        // the kernel builds only frames inside the image (checked again here)
+        if (status[i] != MTCP_GPU_TXB_BUILT || off > buf_len || desc[i].len > buf_len - off) continue;
+        memcpy(static_cast<uint8_t *>(buf) + off, image + off, desc[i].len);
+        ++cnt;
+    }
+    return cnt;
 }
 
 // A staging capacity for `need`: the next power of two once the present one
@@ -1887,10 +1720,10 @@ int mtcp_gpu_tx_build_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *d_seg, uint3
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Built like mtcp_gpu_tx_fill.  Stage 0's chunk buffer holds the frames'
-// image, then the payload, the records, the links and the status bytes; the
-// image is never uploaded (the builder reads no frame byte) and comes back
-// whole into pinned staging, from where only the built frames' bytes reach buf.
+// Stage 0's chunk buffer holds the frames' image, then the payload, the
+// records, the links and the status bytes; the image is never uploaded (the
+// builder reads no frame byte) and comes down pinned, whole, with the status
+// bytes behind it, from where only the built frames' bytes reach buf.
 int mtcp_gpu_tx_build(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *seg, uint32_t n,
                       const void *payload, uint64_t payload_bytes,
                       const mtcp_gpu_tx_link *links, uint32_t n_links,
@@ -1904,59 +1737,31 @@ int mtcp_gpu_tx_build(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *seg, uint32_t n,
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     Stage &s = ctx->stage[0];
-    auto pad = [](uint64_t v) { return (v + 15) & ~15ull; };
     const uint64_t sbytes = (uint64_t)n * sizeof(mtcp_gpu_tx_seg), lbytes = (uint64_t)n_links * sizeof(mtcp_gpu_tx_link);
     const uint64_t dbytes = (uint64_t)n * sizeof(mtcp_gpu_desc);
-    const uint64_t pay_off = pad(buf_len), seg_off = pay_off + pad(payload_bytes), link_off = seg_off + pad(sbytes);
-    const uint64_t st_off = link_off + pad(lbytes), total = st_off + pad(n);
+    const uint64_t pay_off = pad16(buf_len), seg_off = pay_off + pad16(payload_bytes), link_off = seg_off + pad16(sbytes);
+    const uint64_t st_off = link_off + pad16(lbytes), total = st_off + pad16(n);
     // host side: in = payload | records | links | descriptors (bounded calls), out = image | status
-    const uint64_t hin_seg = pad(payload_bytes), hin_link = hin_seg + pad(sbytes), hin_desc = hin_link + pad(lbytes);
-    const uint64_t hin_total = hin_desc + dbytes, hout_total = pay_off + n;
+    const uint64_t hin_total = pad16(payload_bytes) + pad16(sbytes) + pad16(lbytes) + dbytes, hout_total = pay_off + n;
     int rc = stage_reserve(ctx, s, grown(total, s.buf_cap), (uint32_t)grown(n, s.pkt_cap), dl);
     if (rc == MTCP_GPU_OK)
-        rc = stage_host(ctx, s, bounce ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
+        rc = stage_host(ctx, s, dl.bounded ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
     if (rc != MTCP_GPU_OK) return rc;
-    const void *psrc = payload, *ssrc = seg, *lsrc = links, *dsrc = desc;
-    if (bounce) {
-        bounce_in(s.h_in, payload, payload_bytes);
-        memcpy(s.h_in + hin_seg, seg, sbytes);
-        memcpy(s.h_in + hin_link, links, lbytes);
-        memcpy(s.h_in + hin_desc, desc, dbytes);
-        psrc = s.h_in;
-        ssrc = s.h_in + hin_seg;
-        lsrc = s.h_in + hin_link;
-        dsrc = s.h_in + hin_desc;
-    }
-    if ((payload_bytes &&
-         !HIP_OK(hipMemcpyAsync(s.d_buf + pay_off, psrc, payload_bytes, hipMemcpyHostToDevice, s.stream))) ||
-        !HIP_OK(hipMemcpyAsync(s.d_buf + seg_off, ssrc, sbytes, hipMemcpyHostToDevice, s.stream)) ||
-        !HIP_OK(hipMemcpyAsync(s.d_buf + link_off, lsrc, lbytes, hipMemcpyHostToDevice, s.stream)) ||
-        !HIP_OK(hipMemcpyAsync(s.d_desc, dsrc, dbytes, hipMemcpyHostToDevice, s.stream)))
-        rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK)
-        rc = mtcp_gpu_tx_build_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_seg *>(s.d_buf + seg_off), n,
-                                   s.d_buf + pay_off, payload_bytes,
-                                   reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
-                                   buf_len, s.d_desc, off_shift, max_mss, flags, s.d_buf + st_off, s.stream);
-    if (rc == MTCP_GPU_OK &&
-        ((buf_len && !HIP_OK(hipMemcpyAsync(s.h_out, s.d_buf, buf_len, hipMemcpyDeviceToHost, s.stream))) ||
-         !HIP_OK(hipMemcpyAsync(s.h_out + pay_off, s.d_buf + st_off, n, hipMemcpyDeviceToHost, s.stream))))
-        rc = MTCP_GPU_EIO;
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc != MTCP_GPU_OK) return rc;
-    const uint8_t *st = s.h_out + pay_off;
-    uint8_t *out = static_cast<uint8_t *>(buf);
-    uint32_t cnt = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t off = (uint64_t)desc[i].offset << off_shift;
-        // the kernel builds only frames inside the image (checked again here)
-        if (st[i] == MTCP_GPU_TXB_BUILT && off <= buf_len && desc[i].len <= buf_len - off) {
-            memcpy(out + off, s.h_out + off, desc[i].len);
-            ++cnt;
-        }
-    }
+    Call hc(s, dl, {ctx, dl});
+    hc.up(s.d_buf + pay_off, payload, payload_bytes, true);
+    hc.up(s.d_buf + seg_off, seg, sbytes);
+    hc.up(s.d_buf + link_off, links, lbytes);
+    hc.up(s.d_desc, desc, dbytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_tx_build_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_seg *>(s.d_buf + seg_off), n,
+                                      s.d_buf + pay_off, payload_bytes,
+                                      reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
+                                      buf_len, s.d_desc, off_shift, max_mss, flags, s.d_buf + st_off, s.stream));
+    const uint8_t *image = hc.down_pinned(s.d_buf, buf_len);
+    const uint8_t *st = hc.down_pinned(s.d_buf + st_off, n);
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+    const uint32_t cnt = copy_built(buf, image, buf_len, desc, st, n, off_shift);
     memcpy(status, st, n);
     if (n_built) *n_built = cnt;
     return MTCP_GPU_OK;
@@ -1986,14 +1791,13 @@ struct TxSegWork {
     uint64_t first_off, boff_off, pc_off, pb_off, tot_off, bytes;
 };
 TxSegWork txseg_work(uint32_t n) {
-    auto pad = [](uint64_t v) { return (v + 15) & ~15ull; };
     TxSegWork w{};
     w.nwg = (n + mg::kTxsegTile - 1) / mg::kTxsegTile;
     w.first_off = 16ull * n;
-    w.boff_off = w.first_off + pad(4ull * n);
-    w.pc_off = w.boff_off + pad(8ull * n);
-    w.pb_off = w.pc_off + pad(4ull * w.nwg);
-    w.tot_off = w.pb_off + pad(8ull * w.nwg);
+    w.boff_off = w.first_off + pad16(4ull * n);
+    w.pc_off = w.boff_off + pad16(8ull * n);
+    w.pb_off = w.pc_off + pad16(4ull * w.nwg);
+    w.tot_off = w.pb_off + pad16(8ull * w.nwg);
     w.bytes = w.tot_off + 16;
     return w;
 }
@@ -2120,12 +1924,11 @@ int mtcp_gpu_tx_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *d_burst, ui
                                  d_desc, off_shift, max_mss, flags, d_status, stream);
 }
 
-// Built like mtcp_gpu_tx_build.  Stage 0's chunk buffer holds the frames'
-// image, then the payload, the bursts, the links, the segment records, the
-// descriptors, the status bytes, the results, the totals and the workspace;
-// the image is never uploaded and comes back whole into pinned staging with
-// the descriptors, status bytes, results and totals behind it, from where only
-// the built frames' bytes reach buf.
+// Stage 0's chunk buffer holds the frames' image, then the payload, the
+// bursts, the links, the segment records, the descriptors, the status bytes,
+// the results, the totals and the workspace; the image is never uploaded and
+// comes down pinned, whole, with the descriptors, status bytes, results and
+// totals behind it, from where only the built frames' bytes reach buf.
 int mtcp_gpu_tx_send(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *burst, uint32_t n_burst,
                      const void *payload, uint64_t payload_bytes,
                      const mtcp_gpu_tx_link *links, uint32_t n_links,
@@ -2141,9 +1944,7 @@ int mtcp_gpu_tx_send(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *burst, uint32_t
     if (ctx->abandoned) return MTCP_GPU_EIO;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const bool bounce = dl.bounded;
     Stage &s = ctx->stage[0];
-    auto pad = [](uint64_t v) { return (v + 15) & ~15ull; };
     const uint64_t bbytes = (uint64_t)n_burst * sizeof(mtcp_gpu_tx_burst);
     const uint64_t lbytes = (uint64_t)n_links * sizeof(mtcp_gpu_tx_link);
     const uint64_t sbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_tx_seg);
@@ -2151,58 +1952,37 @@ int mtcp_gpu_tx_send(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *burst, uint32_t
     const uint64_t rbytes = (uint64_t)n_burst * sizeof(mtcp_gpu_tx_burst_result);
     const uint64_t wbytes = txseg_work(n_burst).bytes;
     // device: image | payload | bursts | links | records | [descriptors | status | results | totals] | workspace
-    const uint64_t pay_off = pad(buf_len), burst_off = pay_off + pad(payload_bytes), link_off = burst_off + pad(bbytes);
-    const uint64_t seg_off = link_off + pad(lbytes), desc_off = seg_off + pad(sbytes);
-    const uint64_t st_off = desc_off + pad(dbytes), res_off = st_off + pad(seg_cap), tot_off = res_off + pad(rbytes);
+    const uint64_t pay_off = pad16(buf_len), burst_off = pay_off + pad16(payload_bytes), link_off = burst_off + pad16(bbytes);
+    const uint64_t seg_off = link_off + pad16(lbytes), desc_off = seg_off + pad16(sbytes);
+    const uint64_t st_off = desc_off + pad16(dbytes), res_off = st_off + pad16(seg_cap), tot_off = res_off + pad16(rbytes);
     const uint64_t work_off = tot_off + 16, dev_total = work_off + wbytes;
     const uint64_t back = work_off - desc_off;                   // the bracketed part comes back in one copy
     // host side: in = payload | bursts | links (bounded calls), out = image | the bracketed part
-    const uint64_t hin_burst = pad(payload_bytes), hin_link = hin_burst + pad(bbytes), hin_total = hin_link + pad(lbytes);
-    const uint64_t hout_total = pay_off + back;
+    const uint64_t hin_total = pad16(payload_bytes) + pad16(bbytes) + pad16(lbytes), hout_total = pay_off + back;
     int rc = stage_reserve(ctx, s, grown(dev_total, s.buf_cap), 0, dl);
     if (rc == MTCP_GPU_OK)
-        rc = stage_host(ctx, s, bounce ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
+        rc = stage_host(ctx, s, dl.bounded ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
     if (rc != MTCP_GPU_OK) return rc;
-    const void *psrc = payload, *bsrc = burst, *lsrc = links;
-    if (bounce) {
-        bounce_in(s.h_in, payload, payload_bytes);
-        if (bbytes) memcpy(s.h_in + hin_burst, burst, bbytes);
-        memcpy(s.h_in + hin_link, links, lbytes);
-        psrc = s.h_in;
-        bsrc = s.h_in + hin_burst;
-        lsrc = s.h_in + hin_link;
-    }
-    if ((payload_bytes &&
-         !HIP_OK(hipMemcpyAsync(s.d_buf + pay_off, psrc, payload_bytes, hipMemcpyHostToDevice, s.stream))) ||
-        (bbytes && !HIP_OK(hipMemcpyAsync(s.d_buf + burst_off, bsrc, bbytes, hipMemcpyHostToDevice, s.stream))) ||
-        !HIP_OK(hipMemcpyAsync(s.d_buf + link_off, lsrc, lbytes, hipMemcpyHostToDevice, s.stream)))
-        rc = MTCP_GPU_EIO;
-    if (rc == MTCP_GPU_OK)
-        rc = mtcp_gpu_tx_send_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_burst *>(s.d_buf + burst_off), n_burst,
-                                  s.d_buf + pay_off, payload_bytes,
-                                  reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
-                                  buf_off, buf_len, off_shift, slot_bytes, max_mss, flags,
-                                  reinterpret_cast<mtcp_gpu_tx_seg *>(s.d_buf + seg_off),
-                                  reinterpret_cast<mtcp_gpu_desc *>(s.d_buf + desc_off), seg_cap,
-                                  reinterpret_cast<mtcp_gpu_tx_burst_result *>(s.d_buf + res_off),
-                                  reinterpret_cast<uint64_t *>(s.d_buf + tot_off), s.d_buf + st_off,
-                                  s.d_buf + work_off, wbytes, s.stream);
-    if (rc == MTCP_GPU_OK &&
-        ((buf_len && !HIP_OK(hipMemcpyAsync(s.h_out, s.d_buf, buf_len, hipMemcpyDeviceToHost, s.stream))) ||
-         !HIP_OK(hipMemcpyAsync(s.h_out + pay_off, s.d_buf + desc_off, back, hipMemcpyDeviceToHost, s.stream))))
-        rc = MTCP_GPU_EIO;
-    rc = finish_call(ctx, rc, dl, 1);
-    if (rc != MTCP_GPU_OK) return rc;
-    const uint8_t *hb = s.h_out + pay_off;
+    Call hc(s, dl, {ctx, dl});
+    hc.up(s.d_buf + pay_off, payload, payload_bytes, true);
+    hc.up(s.d_buf + burst_off, burst, bbytes);
+    hc.up(s.d_buf + link_off, links, lbytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_tx_send_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_burst *>(s.d_buf + burst_off), n_burst,
+                                     s.d_buf + pay_off, payload_bytes,
+                                     reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
+                                     buf_off, buf_len, off_shift, slot_bytes, max_mss, flags,
+                                     reinterpret_cast<mtcp_gpu_tx_seg *>(s.d_buf + seg_off),
+                                     reinterpret_cast<mtcp_gpu_desc *>(s.d_buf + desc_off), seg_cap,
+                                     reinterpret_cast<mtcp_gpu_tx_burst_result *>(s.d_buf + res_off),
+                                     reinterpret_cast<uint64_t *>(s.d_buf + tot_off), s.d_buf + st_off,
+                                     s.d_buf + work_off, wbytes, s.stream));
+    const uint8_t *image = hc.down_pinned(s.d_buf, buf_len);
+    const uint8_t *hb = hc.down_pinned(s.d_buf + desc_off, back);
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
     const mtcp_gpu_desc *hd = reinterpret_cast<const mtcp_gpu_desc *>(hb);
     const uint8_t *hs = hb + (st_off - desc_off);
-    uint8_t *out = static_cast<uint8_t *>(buf);
-    for (uint32_t k = 0; k < seg_cap; ++k) {
-        const uint64_t off = (uint64_t)hd[k].offset << off_shift;
-        // the kernel builds only frames inside the image (checked again here)
-        if (hs[k] == MTCP_GPU_TXB_BUILT && off <= buf_len && hd[k].len <= buf_len - off)
-            memcpy(out + off, s.h_out + off, hd[k].len);
-    }
+    copy_built(buf, image, buf_len, hd, hs, seg_cap, off_shift);
     memcpy(desc, hd, dbytes);
     memcpy(status, hs, seg_cap);
     if (rbytes) memcpy(res, hb + (res_off - desc_off), rbytes);
@@ -2262,42 +2042,38 @@ int mtcp_gpu_addr_pool_search(mtcp_gpu_ctx *ctx, int core, int num_queues, uint3
     hipStream_t st = ctx->stream;
     const Deadline dl(ctx->wait_us);
     Stage &s0 = ctx->stage[0];                                             // its stream is st
+    Call hc(s0, dl, {ctx, dl});
     const uint32_t saddr_base_h = __builtin_bswap32(saddr_base);           // addr_pool.c:150
-    int rc = mtcp_gpu_rss_queue_map_dev(ctx, saddr_base_h, (uint32_t)num_addr,
-                                        __builtin_bswap32(daddr),
-                                        (uint16_t)((dport >> 8) | (dport << 8)), num_queues,
-                                        endian_check, d_queue, st);
-    // what comes back lands in the stage's pinned buffer first (the count,
-    // then the entries), copied out once its copy has finished
-    if (rc == MTCP_GPU_OK) rc = stage_host(ctx, s0, 0, 8ull * std::max(limit, 1u), dl);
-    if (rc == MTCP_GPU_OK) {
+    hc.note(mtcp_gpu_rss_queue_map_dev(ctx, saddr_base_h, (uint32_t)num_addr, __builtin_bswap32(daddr),
+                                       (uint16_t)((dport >> 8) | (dport << 8)), num_queues, endian_check, d_queue,
+                                       st));
+    // what comes back comes down pinned (the count, then the entries),
+    // copied out once its copy has finished
+    if (hc.ok()) hc.note(stage_host(ctx, s0, 0, 8ull * std::max(limit, 1u), dl));
+    if (hc.ok()) {
         hipLaunchKernelGGL(mg::pool_count_kernel, dim3(nb), dim3(mg::kBlock), 0, st, d_queue, total,
                            (uint32_t)core, d_counts);
         hipLaunchKernelGGL(mg::pool_scan_kernel, dim3(1), dim3(mg::kBlock), 0, st, d_counts, nb);
         if (limit)
             hipLaunchKernelGGL(mg::pool_emit_kernel, dim3(nb), dim3(mg::kBlock), 0, st, d_queue,
                                total, (uint32_t)core, d_counts, saddr_base_h, limit, d_out);
-        if (!HIP_OK(hipGetLastError()) ||
-            !HIP_OK(hipMemcpyAsync(s0.h_out, d_counts + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, st)))
-            rc = MTCP_GPU_EIO;
-        rc = finish_call(ctx, rc, dl, 1);
+        if (!HIP_OK(hipGetLastError())) hc.note(MTCP_GPU_EIO);
     }
+    const uint8_t *h_count = hc.down_pinned(d_counts + nb, sizeof(uint32_t));
+    int rc = hc.finish();                                    // after a failure too: d_mem is released below
     if (rc == MTCP_GPU_OK) {
         uint32_t count;
-        memcpy(&count, s0.h_out, sizeof(count));
+        memcpy(&count, h_count, sizeof(count));
         const uint32_t kept = std::min(count, num_entry);
         const uint32_t copy = std::min(kept, max_out);
-        if (copy && !HIP_OK(hipMemcpyAsync(s0.h_out, d_out, (size_t)copy * sizeof(mtcp_gpu_addr_entry),
-                                           hipMemcpyDeviceToHost, st)))
-            rc = MTCP_GPU_EIO;
-        rc = finish_call(ctx, rc, dl, 1);
+        const uint8_t *h_ent = hc.down_pinned(d_out, (size_t)copy * sizeof(mtcp_gpu_addr_entry));
+        rc = hc.finish();
         if (rc == MTCP_GPU_OK) {
-            memcpy(out, s0.h_out, (size_t)copy * sizeof(mtcp_gpu_addr_entry));
+            if (copy) memcpy(out, h_ent, (size_t)copy * sizeof(mtcp_gpu_addr_entry));
             *n_found = kept;
         }
     }
     if (rc == MTCP_GPU_ETIMEDOUT) return rc;                 // abandoned: d_mem stays allocated
-    if (rc != MTCP_GPU_OK) (void)finish_call(ctx, rc, dl, 1);
     if (!ctx->abandoned) mtcp_park::release(d_mem, bytes, mtcp_park::kDevice, !dl.bounded);
     return rc;
 }

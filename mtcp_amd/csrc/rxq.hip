@@ -78,24 +78,6 @@ inline void serve_prefetch(const void *p, uint32_t hint) {
 }
 }  // namespace
 
-namespace {
-
-// the rxq's device is current for one call; the caller's is restored
-struct RxqDevice {
-    int prev = -1;
-    bool ok = false;
-    explicit RxqDevice(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = prev == device || hipSetDevice(device) == hipSuccess;
-    }
-    ~RxqDevice() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 int mtcp_gpu_rxq_create(mtcp_gpu_rxq **out, mtcp_gpu_ctx *ctx, uint32_t max_pkts,
@@ -106,7 +88,7 @@ int mtcp_gpu_rxq_create(mtcp_gpu_rxq **out, mtcp_gpu_ctx *ctx, uint32_t max_pkts
     hipDevice_t dev = 0;
     if (hipStreamGetDevice(reinterpret_cast<hipStream_t>(mtcp_gpu_stream(ctx)), &dev) != hipSuccess)
         return MTCP_GPU_ENODEV;
-    RxqDevice dg(dev);
+    DeviceGuard dg(dev);
     if (!dg.ok) return MTCP_GPU_ENODEV;
     mtcp_gpu_rxq *q = new (std::nothrow) mtcp_gpu_rxq;
     if (!q) return MTCP_GPU_ENOMEM;
@@ -166,7 +148,7 @@ int mtcp_gpu_rxq_create(mtcp_gpu_rxq **out, mtcp_gpu_ctx *ctx, uint32_t max_pkts
 
 void mtcp_gpu_rxq_destroy(mtcp_gpu_rxq *q) {
     if (!q) return;
-    RxqDevice dg(q->device);
+    DeviceGuard dg(q->device);
     if (q->evt && (q->abandoned || (q->inflight && mg_ctx_abandoned(q->ctx)))) {
         // a flush rxq_wait_for gave up on may still copy into buf / res /
         // d_out: wait for it a bounded time; if the device still has not
@@ -245,7 +227,7 @@ int mtcp_gpu_rxq_flush_async(mtcp_gpu_rxq *q) {
     if (!q || q->inflight) return MTCP_GPU_EINVAL;
     if (q->abandoned || mg_ctx_abandoned(q->ctx)) return MTCP_GPU_EIO;
     if (q->n == q->done_n) return MTCP_GPU_OK;
-    RxqDevice dg(q->device);
+    DeviceGuard dg(q->device);
     if (!dg.ok) return MTCP_GPU_ENODEV;
     const uint32_t first = q->done_n, cnt = q->n - q->done_n;
     // frames staged since the last flush: their descriptors are relative to
@@ -288,7 +270,7 @@ int mtcp_gpu_rxq_wait_for(mtcp_gpu_rxq *q, uint32_t *n, uint32_t timeout_us) {
     if (!q) return MTCP_GPU_EINVAL;
     int rc = MTCP_GPU_OK;
     if (q->inflight) {
-        RxqDevice dg(q->device);
+        DeviceGuard dg(q->device);
         // (a context abandoned meanwhile, e.g. by a tx fill that timed out on
         // the same stream, is not waited on: one look at the event)
         uint32_t lim = timeout_us ? timeout_us : q->wait_us;
