@@ -20,7 +20,8 @@
  * a host thread can take one stream and walk it.
  *
  * Stability is the contract: two segments of one stream come out in the order
- * they went in.  Nothing behind the grouping is built here.
+ * they went in.  Nothing behind the grouping is built here; its first consumer,
+ * the receive walk of every stream's list, is mtcp_gpu_rcvwalk.h.
  *
  * Plain C, as mtcp_gpu.h; MTCP_GPU_ABI_VERSION is unchanged (nothing that
  * exists changes): test for MTCP_GPU_HAS_GROUP.

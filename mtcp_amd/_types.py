@@ -108,3 +108,22 @@ FLOW_MISS = 0xFFFFFFFE
 FLOWTAB_MAX_ID = 0xFFFFFFEF
 FLOWTAB_MIN_CAP_LOG2, FLOWTAB_MAX_CAP_LOG2, FLOWTAB_MAX_BATCH = 4, 26, 1 << 26
 MIN_PORT, MAX_PORT = 1025, 65536   # mtcp/src/include/addr_pool.h:7-8
+
+# include/mtcp_gpu_rcvwalk.h: struct mtcp_gpu_rcv_state (one stream's receive
+# state: what ValidateSequence, ProcessTCPPayload and RBPut read and write of it,
+# tcp_in.c:101-179, :537-610, tcp_ring_buffer.c:280-382) and struct
+# mtcp_gpu_rcv_place (one packet's placement record)
+RCV_STATE_DTYPE = np.dtype([
+    ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("head_seq", "<u4"), ("merged_len", "<u4"), ("size", "<u4"),
+    ("ts_recent", "<u4"), ("ts_lastack_rcvd", "<u4"), ("tcp_state", "u1"), ("saw_timestamp", "u1"), ("nfrag", "u1"),
+    ("rsvd", "u1"), ("frag", [("seq", "<u4"), ("len", "<u4")], (4,)),
+])
+RCV_PLACE_DTYPE = np.dtype([("put_off", "<u4"), ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("put_len", "<u2"),
+                            ("verdict", "u1"), ("flags", "u1")])
+assert RCV_STATE_DTYPE.itemsize == 64 and RCV_PLACE_DTYPE.itemsize == 16
+assert [RCV_STATE_DTYPE.fields[f][1] for f in RCV_STATE_DTYPE.names] == [0, 4, 8, 12, 16, 20, 24, 28, 29, 30, 31, 32]
+RCV_COPY, RCV_ACK_NOW, RCV_ACK_AGGREGATE, RCV_READ_EVENT, RCV_TS_NEWER = 0x01, 0x02, 0x04, 0x08, 0x10
+RCV_VERDICTS = ("NONE", "DEFER_STATE", "DEFER_BAD_STATE", "DEFER_FLAGS", "DEFER_TS", "DEFER_FRAG_FULL", "DEFER_BEHIND",
+                "PAWS_NO_TS", "PAWS_OLD", "SEQ_WINPROBE", "SEQ_OLD", "SEQ_AHEAD", "ACK_ONLY", "PUT_DROPPED",
+                "PUT_NO_ROOM", "PUT_STORED")
+RCV_MAX_FRAGS, RCV_MAX_SIZE, RCV_ST_ESTABLISHED = 4, 1 << 30, 4

@@ -6,6 +6,7 @@
 // software path exactly as dev_ioctl returning -1 would make it
 // (mtcp/src/ip_in.c:29-31, tcp_in.c:1160-1164).
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -17,6 +18,7 @@
 #include "../../include/mtcp_gpu.h"
 #include "../../include/mtcp_gpu_flowtab.h"
 #include "../../include/mtcp_gpu_group.h"
+#include "../../include/mtcp_gpu_rcvwalk.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
 #include "../../include/mtcp_gpu_txbuild.h"
@@ -29,6 +31,7 @@
 #include "host_call.hpp"
 #include "host_copy.hpp"
 #include "park.hpp"
+#include "rcvwalk_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
 #include "steer_kernels.hpp"
@@ -1406,6 +1409,116 @@ int mtcp_gpu_group(mtcp_gpu_ctx *ctx, const uint32_t *sid, uint32_t n, uint32_t 
     const uint32_t m = std::min(nseg[0], n);
     hc.down(seg_sid, d_seg_sid, (size_t)m * sizeof(uint32_t));
     hc.down(seg_start, d_seg_start, ((size_t)m + 1) * sizeof(uint32_t));
+    return hc.finish();
+}
+
+// ---- the per-stream receive walk -------------------------------
+static_assert(sizeof(mtcp_gpu_rcv_state) == 64 && sizeof(mtcp_gpu_rcv_place) == 16, "mtcp_gpu_rcvwalk.h layouts");
+static_assert(offsetof(mtcp_gpu_rcv_state, tcp_state) == 28 && offsetof(mtcp_gpu_rcv_state, frag) == 32 &&
+              offsetof(mtcp_gpu_rcv_place, put_len) == 12 && offsetof(mtcp_gpu_rcv_place, verdict) == 14,
+              "rcvwalk_kernels.hpp reads and writes the records as 16 B pieces");
+static_assert(offsetof(mtcp_gpu_result, seq) == 12 && offsetof(mtcp_gpu_result, payload_len) == 32 &&
+              offsetof(mtcp_gpu_result, tcp_flags) == 35, "rcvwalk_gather_kernel's two loads of a record");
+
+uint32_t mtcp_gpu_rcvwalk_short_len(void) { return mg::kRcvShortLen; }
+
+uint64_t mtcp_gpu_rcvwalk_work_bytes(uint32_t n, uint32_t max_id) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return 0;
+    return mg::rcv_work(n).bytes;
+}
+
+int mtcp_gpu_rcvwalk_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, const mtcp_gpu_tcpopt *d_opt,
+                         uint32_t n, uint32_t max_id, const uint32_t *d_idx, const uint32_t *d_seg_sid,
+                         const uint32_t *d_seg_start, const uint32_t *d_nseg, mtcp_gpu_rcv_state *d_state,
+                         mtcp_gpu_rcv_place *d_place, uint32_t *d_seg_stop, void *d_work, uint64_t work_bytes,
+                         void *stream) {
+    if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
+        (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        (n && (!d_res || !d_idx || !d_seg_sid || !d_seg_start || !d_nseg || !d_state || !d_place || !d_seg_stop ||
+               !d_work)) ||
+        ((uintptr_t)d_res & 7) || ((uintptr_t)d_opt & 15) || ((uintptr_t)d_idx & 3) || ((uintptr_t)d_seg_sid & 3) ||
+        ((uintptr_t)d_seg_start & 3) || ((uintptr_t)d_nseg & 3) || ((uintptr_t)d_state & 63) ||
+        ((uintptr_t)d_place & 15) || ((uintptr_t)d_seg_stop & 3) || ((uintptr_t)d_work & 15))
+        return MTCP_GPU_EINVAL;
+    const mg::RcvWork w = mg::rcv_work(n);
+    if (n && work_bytes < w.bytes) return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const dim3 block(mg::kBlock), grid((n + mg::kBlock - 1) / mg::kBlock);
+    uint4 *win = reinterpret_cast<uint4 *>(static_cast<uint8_t *>(d_work) + w.in_off);
+    hipLaunchKernelGGL(mg::rcvwalk_gather_kernel, grid, block, 0, st, reinterpret_cast<const uint8_t *>(d_res),
+                       reinterpret_cast<const uint4 *>(d_opt), d_idx, n, win, reinterpret_cast<uint4 *>(d_place));
+    hipLaunchKernelGGL((mg::rcvwalk_walk_kernel<mg::kRcvShortLen, mg::kRcvWaveMax>), grid, block, 0, st, win, d_idx, n, max_id,
+                       d_seg_sid, d_seg_start, d_nseg, d_opt ? 1u : 0u, reinterpret_cast<uint4 *>(d_state),
+                       reinterpret_cast<uint4 *>(d_place), d_seg_stop);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+// Stage 0's chunk buffer holds the inputs (res, opt, idx, seg_sid[m],
+// seg_start[m + 1], nseg, each padded to 16 B), then in one piece what comes
+// back (state[max_id + 1] at a 64 B boundary, place[n], seg_stop[n]), then the
+// workspace.  A bounded call brings the piece down pinned in one wait and
+// copies out what the contract names: nothing has reached the caller when it
+// gives up.
+int mtcp_gpu_rcvwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_gpu_tcpopt *opt, uint32_t n,
+                     uint32_t max_id, const uint32_t *idx, const uint32_t *seg_sid, const uint32_t *seg_start,
+                     const uint32_t *nseg, mtcp_gpu_rcv_state *state, mtcp_gpu_rcv_place *place,
+                     uint32_t *seg_stop) {
+    if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
+        (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        (n && (!res || !idx || !seg_sid || !seg_start || !nseg || !state || !place || !seg_stop)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const uint32_t m = std::min(nseg[0], n);
+    const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_result), obytes = opt ? (uint64_t)n * sizeof(mtcp_gpu_tcpopt) : 0;
+    const uint64_t ibytes = (uint64_t)n * sizeof(uint32_t), mbytes = (uint64_t)m * sizeof(uint32_t);
+    const uint64_t sbytes = ((uint64_t)max_id + 1) * sizeof(mtcp_gpu_rcv_state);
+    const uint64_t pbytes = (uint64_t)n * sizeof(mtcp_gpu_rcv_place);
+    const uint64_t res_off = 0, opt_off = res_off + pad16(rbytes), idx_off = opt_off + pad16(obytes);
+    const uint64_t sid_off = idx_off + pad16(ibytes), start_off = sid_off + pad16(mbytes);
+    const uint64_t nseg_off = start_off + pad16(mbytes + 4);
+    const uint64_t state_off = (nseg_off + 16 + 63) & ~63ull, place_off = state_off + sbytes;
+    const uint64_t stop_off = place_off + pbytes, back_bytes = sbytes + pbytes + ibytes;
+    const uint64_t work_off = pad16(stop_off + ibytes), wbytes = mg::rcv_work(n).bytes;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, work_off + wbytes, 0, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, state_off + sbytes, back_bytes, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    auto at = [&](uint64_t off) { return s.d_buf + off; };
+    mtcp_gpu_rcv_state *d_state = reinterpret_cast<mtcp_gpu_rcv_state *>(at(state_off));
+    Call hc(s, dl, {ctx, dl});
+    hc.up(at(res_off), res, rbytes);
+    if (opt) hc.up(at(opt_off), opt, obytes);
+    hc.up(at(idx_off), idx, ibytes);
+    hc.up(at(sid_off), seg_sid, mbytes);
+    hc.up(at(start_off), seg_start, mbytes + 4);
+    hc.up(at(nseg_off), &m, sizeof(uint32_t));
+    hc.up(d_state, state, sbytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_rcvwalk_dev(ctx, reinterpret_cast<const mtcp_gpu_result *>(at(res_off)),
+                                     opt ? reinterpret_cast<const mtcp_gpu_tcpopt *>(at(opt_off)) : nullptr, n, max_id,
+                                     reinterpret_cast<const uint32_t *>(at(idx_off)),
+                                     reinterpret_cast<const uint32_t *>(at(sid_off)),
+                                     reinterpret_cast<const uint32_t *>(at(start_off)),
+                                     reinterpret_cast<const uint32_t *>(at(nseg_off)), d_state,
+                                     reinterpret_cast<mtcp_gpu_rcv_place *>(at(place_off)),
+                                     reinterpret_cast<uint32_t *>(at(stop_off)), at(work_off), wbytes, s.stream));
+    if (hc.bounded()) {
+        const uint8_t *h = hc.down_pinned(d_state, back_bytes);
+        if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+        memcpy(state, h, sbytes);
+        memcpy(place, h + sbytes, pbytes);
+        memcpy(seg_stop, h + sbytes + pbytes, mbytes);
+        return rc;
+    }
+    hc.down(state, d_state, sbytes);
+    hc.down(place, at(place_off), pbytes);
+    hc.down(seg_stop, at(stop_off), mbytes);
     return hc.finish();
 }
 

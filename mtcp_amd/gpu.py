@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -334,6 +334,47 @@ class Context:
                                    seg_start.ctypes.data, nseg.ctypes.data), "mtcp_gpu_group")
         m = int(nseg[0])
         return idx, seg_sid[:m], seg_start[:m + 1]
+
+    # -- the per-stream receive walk (tcp_in.c:101-179, :537-610, tcp_ring_buffer.c:280-382; mtcp_gpu_rcvwalk.h) --
+    @staticmethod
+    def rcvwalk_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_rcvwalk_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_rcvwalk_work_bytes(n, max_id)
+
+    @staticmethod
+    def rcvwalk_short_len() -> int:
+        return lib().mtcp_gpu_rcvwalk_short_len()
+
+    def rcvwalk_dev(self, res, opt, n: int, max_id: int, idx, seg_sid, seg_start, nseg, state, place, seg_stop,
+                    work, stream=None) -> None:
+        """res: n x 40 B records; opt: n x 16 B option records or None; idx,
+        seg_sid, seg_start, nseg: as group_dev wrote them; state: (max_id + 1) x
+        64 B (RCV_STATE_DTYPE), updated; place: n x 16 B (RCV_PLACE_DTYPE);
+        seg_stop: n x u32; work: at least rcvwalk_work_bytes(n, max_id) bytes."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_rcvwalk_dev(self._h, _dptr(res), None if opt is None else _dptr(opt), n, max_id,
+                                             _dptr(idx), _dptr(seg_sid), _dptr(seg_start), _dptr(nseg), _dptr(state),
+                                             _dptr(place), _dptr(seg_stop), _dptr(work),
+                                             work.numel() * work.element_size(), st), "mtcp_gpu_rcvwalk_dev")
+
+    def rcvwalk(self, res: np.ndarray, opt, max_id: int, idx: np.ndarray, seg_sid: np.ndarray,
+                seg_start: np.ndarray, state: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """mtcp_gpu_rcvwalk over the arrays group() returned: `state`
+        ((max_id + 1) x RCV_STATE_DTYPE) is updated in place; returns (place,
+        seg_stop), seg_stop cut to the table's m entries."""
+        res = np.ascontiguousarray(res, dtype=RESULT_DTYPE)
+        if opt is not None:
+            opt = np.ascontiguousarray(opt, dtype=TCPOPT_DTYPE)
+        n, m = len(res), len(seg_sid)
+        if state.dtype != RCV_STATE_DTYPE or not state.flags.c_contiguous or len(state) != max_id + 1:
+            raise ValueError("state: (max_id + 1) contiguous RCV_STATE_DTYPE records")
+        idx, seg_sid = np.ascontiguousarray(idx, dtype=np.uint32), np.ascontiguousarray(seg_sid, dtype=np.uint32)
+        seg_start, nseg = np.ascontiguousarray(seg_start, dtype=np.uint32), np.array([m], dtype=np.uint32)
+        place, seg_stop = np.zeros(n, dtype=RCV_PLACE_DTYPE), np.zeros(max(m, 1), dtype=np.uint32)
+        check(lib().mtcp_gpu_rcvwalk(self._h, res.ctypes.data, None if opt is None else opt.ctypes.data, n, max_id,
+                                     idx.ctypes.data, seg_sid.ctypes.data, seg_start.ctypes.data, nseg.ctypes.data,
+                                     state.ctypes.data, place.ctypes.data, seg_stop.ctypes.data), "mtcp_gpu_rcvwalk")
+        return place, seg_stop[:m]
 
     # -- tx frames from segment records (tcp_out.c:135-354; mtcp_gpu_txbuild.h) --
     def tx_build_dev(self, seg, n: int, payload, links, buf, desc, off_shift: int, status,
