@@ -6,12 +6,12 @@ The product is libmtcp_gpu.so (HIP kernels + the C ABI of include/mtcp_gpu.h);
 this package is its Python view for tests and benchmarks.
 """
 from ._types import (DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOW_MISS, FLOW_NONE, RESULT16_DTYPE, RESULT_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE,  # noqa: F401
-                     RCV_VERDICTS, RX_ERROR_VERDICTS,
+                     RCV_BUF_DTYPE, RCVCOPY_STATS, RCV_VERDICTS, RX_ERROR_VERDICTS,
                      STEER_DROP_BAD, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE,
                      TX_SEG_DTYPE, VERDICTS, compact_of)
 from . import pktgen  # noqa: F401
 
 __all__ = ["DESC_DTYPE", "FLOW_ENTRY_DTYPE", "FLOW_MISS", "FLOW_NONE", "RESULT_DTYPE", "RESULT16_DTYPE", "VERDICTS", "RX_ERROR_VERDICTS",
            "STEER_DROP_BAD", "TCPOPT_DTYPE", "TX_SEG_DTYPE", "TX_LINK_DTYPE", "TX_BURST_DTYPE",
-           "TX_BURST_RESULT_DTYPE", "RCV_STATE_DTYPE", "RCV_PLACE_DTYPE", "RCV_VERDICTS", "compact_of", "pktgen"]
+           "TX_BURST_RESULT_DTYPE", "RCV_STATE_DTYPE", "RCV_PLACE_DTYPE", "RCV_VERDICTS", "RCV_BUF_DTYPE", "RCVCOPY_STATS", "compact_of", "pktgen"]
 # `from mtcp_amd import gpu` loads libmtcp_gpu.so (and raises if it was not built).

@@ -35,6 +35,7 @@ EXPORTS = (
     "mtcp_gpu_flowtab_lookup", "mtcp_gpu_flowtab_stats", "mtcp_gpu_flowtab_rehash",
     "mtcp_gpu_group_tile", "mtcp_gpu_group_work_bytes", "mtcp_gpu_group_dev", "mtcp_gpu_group",
     "mtcp_gpu_rcvwalk_work_bytes", "mtcp_gpu_rcvwalk_short_len", "mtcp_gpu_rcvwalk_dev", "mtcp_gpu_rcvwalk",
+    "mtcp_gpu_rcvcopy_work_bytes", "mtcp_gpu_rcvcopy_dev",
     "mtcp_gpu_rxq_pending", "mtcp_gpu_rxq_flush", "mtcp_gpu_rxq_flush_async", "mtcp_gpu_rxq_wait", "mtcp_gpu_rxq_wait_for", "mtcp_gpu_rxq_get", "mtcp_gpu_rxq_get16", "mtcp_gpu_rxq_frame", "mtcp_gpu_rxq_reset",
 )
 
@@ -132,6 +133,9 @@ def lib() -> ctypes.CDLL:
         "mtcp_gpu_rcvwalk_short_len": ([], u32),
         "mtcp_gpu_rcvwalk_dev": ([vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp], i32),
         "mtcp_gpu_rcvwalk": ([vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mtcp_gpu_rcvcopy_work_bytes": ([u32, u32], u64),
+        "mtcp_gpu_rcvcopy_dev": ([vp, vp, u64, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64,
+                                  vp], i32),
         "mtcp_gpu_pktgen_dev": ([vp, u64, vp, u32, u32, u64, u64, vp], i32),
         "mtcp_gpu_rxq_create": ([ctypes.POINTER(vp), vp, u32, u64], i32),
         "mtcp_gpu_rxq_destroy": ([vp], None),

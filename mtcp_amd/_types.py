@@ -127,3 +127,13 @@ RCV_VERDICTS = ("NONE", "DEFER_STATE", "DEFER_BAD_STATE", "DEFER_FLAGS", "DEFER_
                 "PAWS_NO_TS", "PAWS_OLD", "SEQ_WINPROBE", "SEQ_OLD", "SEQ_AHEAD", "ACK_ONLY", "PUT_DROPPED",
                 "PUT_NO_ROOM", "PUT_STORED")
 RCV_MAX_FRAGS, RCV_MAX_SIZE, RCV_ST_ESTABLISHED = 4, 1 << 30, 4
+
+# include/mtcp_gpu_rcvcopy.h: struct mtcp_gpu_rcv_buf (one stream's receive
+# buffer in the arena: what RBPut's byte work reads and writes of it,
+# tcp_ring_buffer.c:304-319) and the status bytes of d_cstat
+RCV_BUF_DTYPE = np.dtype([("data_off", "<u8"), ("size", "<u4"), ("head_offset", "<u4"), ("tail_offset", "<u4"),
+                          ("last_len", "<u4"), ("rsvd", "<u4", (2,))])
+assert RCV_BUF_DTYPE.itemsize == 32
+assert [RCV_BUF_DTYPE.fields[f][1] for f in RCV_BUF_DTYPE.names] == [0, 8, 12, 16, 20, 24]
+RCVCOPY_STATS = ("NONE", "FRONT", "ORDERED", "BAD_BUF", "BAD_SRC", "BAD_RANGE")
+RCVCOPY_WAVE_LEN = 64

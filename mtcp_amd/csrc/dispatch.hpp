@@ -223,4 +223,18 @@ inline int txbuild_group(uint64_t payload_bytes, uint32_t n) {
            : avg <= kTxBuildHalfUpToPayload ? 32 : 64;
 }
 
+// The receive copy (rcvcopy_kernels.hpp) puts a group of G
+// lanes on every position of the batch, FRONT packet or not.  Payload lengths
+// are known on the device only and the launch waits for nothing, so the choice
+// is by the batch's average slot, buf_len / n, which bounds the average
+// payload: eight lanes (128 B of buffer per pass) while a slot holds a few
+// passes of them, half a wave (512 B per pass: an MSS payload of 1 448 B is 91
+// or 92 chunks, three passes) above.  The widths rest on these byte counts;
+// tools/rcvcopy_bench.py measures both.
+constexpr uint64_t kRcvCopyOctUpToSlot = 512;
+inline int rcvcopy_group(uint64_t buf_len, uint32_t n) {
+    const uint64_t avg = n ? buf_len / n : 0;
+    return avg <= kRcvCopyOctUpToSlot ? 8 : 32;
+}
+
 }  // namespace

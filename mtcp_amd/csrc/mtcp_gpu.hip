@@ -19,6 +19,7 @@
 #include "../../include/mtcp_gpu_flowtab.h"
 #include "../../include/mtcp_gpu_group.h"
 #include "../../include/mtcp_gpu_rcvwalk.h"
+#include "../../include/mtcp_gpu_rcvcopy.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
 #include "../../include/mtcp_gpu_txbuild.h"
@@ -32,6 +33,7 @@
 #include "host_copy.hpp"
 #include "park.hpp"
 #include "rcvwalk_kernels.hpp"
+#include "rcvcopy_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
 #include "steer_kernels.hpp"
@@ -1520,6 +1522,60 @@ int mtcp_gpu_rcvwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_g
     hc.down(place, at(place_off), pbytes);
     hc.down(seg_stop, at(stop_off), mbytes);
     return hc.finish();
+}
+
+// ---- the payload copy behind the walk ---------------------------
+static_assert(sizeof(mtcp_gpu_rcv_buf) == 32 && offsetof(mtcp_gpu_rcv_buf, size) == 8 &&
+              offsetof(mtcp_gpu_rcv_buf, tail_offset) == 16 && offsetof(mtcp_gpu_rcv_buf, rsvd) == 24,
+              "rcvcopy_plan_kernel reads and writes a record as two 16 B pieces");
+static_assert(sizeof(mtcp_gpu_desc) == 8 && offsetof(mtcp_gpu_desc, len) == 4 &&
+              offsetof(mtcp_gpu_result, ihl_doff) == 34, "rcvcopy_prep_kernel's loads");
+
+uint64_t mtcp_gpu_rcvcopy_work_bytes(uint32_t n, uint32_t max_id) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return 0;
+    return mg::copy_work(n).bytes;
+}
+
+int mtcp_gpu_rcvcopy_dev(mtcp_gpu_ctx *ctx, const void *d_buf, uint64_t buf_len, const mtcp_gpu_desc *d_desc,
+                         uint32_t off_shift, const mtcp_gpu_result *d_res, const mtcp_gpu_rcv_place *d_place,
+                         uint32_t n, uint32_t max_id, const uint32_t *d_idx, const uint32_t *d_seg_sid,
+                         const uint32_t *d_seg_start, const uint32_t *d_nseg, const uint32_t *d_seg_stop,
+                         mtcp_gpu_rcv_buf *d_rbuf, void *d_arena, uint64_t arena_bytes, uint8_t *d_cstat,
+                         void *d_work, uint64_t work_bytes, void *stream) {
+    if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
+        (ctx->flags & MTCP_GPU_F_COMPACT) || off_shift > 16 || (buf_len & 15) ||
+        (n && (!d_buf || !d_desc || !d_res || !d_place || !d_idx || !d_seg_sid || !d_seg_start || !d_nseg ||
+               !d_seg_stop || !d_rbuf || !d_arena || !d_cstat || !d_work)) ||
+        ((uintptr_t)d_buf & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_res & 7) || ((uintptr_t)d_place & 15) ||
+        ((uintptr_t)d_idx & 3) || ((uintptr_t)d_seg_sid & 3) || ((uintptr_t)d_seg_start & 3) ||
+        ((uintptr_t)d_nseg & 3) || ((uintptr_t)d_seg_stop & 3) || ((uintptr_t)d_rbuf & 31) ||
+        ((uintptr_t)d_arena & 15) || ((uintptr_t)d_work & 15))
+        return MTCP_GPU_EINVAL;
+    const mg::CopyWork w = mg::copy_work(n);
+    if (n && work_bytes < w.bytes) return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const dim3 block(mg::kBlock), grid((n + mg::kBlock - 1) / mg::kBlock);
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint4 *win = reinterpret_cast<uint4 *>(work + w.in_off), *wsum = reinterpret_cast<uint4 *>(work + w.sum_off);
+    uint2 *wplan = reinterpret_cast<uint2 *>(work + w.plan_off);
+    const uint64_t buf = reinterpret_cast<uint64_t>(d_buf), arena = reinterpret_cast<uint64_t>(d_arena);
+    hipLaunchKernelGGL(mg::rcvcopy_prep_kernel, grid, block, 0, st, reinterpret_cast<const uint8_t *>(d_res),
+                       reinterpret_cast<const uint4 *>(d_place), reinterpret_cast<const uint2 *>(d_desc), off_shift,
+                       buf_len, d_idx, n, win, wplan, d_cstat);
+    hipLaunchKernelGGL(mg::rcvcopy_plan_kernel, grid, block, 0, st, win, d_idx, n, max_id, d_seg_sid, d_seg_start,
+                       d_nseg, d_seg_stop, reinterpret_cast<uint4 *>(d_rbuf), arena, arena_bytes, wplan, wsum, d_cstat);
+    const int group = rcvcopy_group(buf_len, n);
+    const dim3 fgrid((uint32_t)(((uint64_t)n * group + mg::kBlock - 1) / mg::kBlock));
+    if (group == 8)
+        hipLaunchKernelGGL(mg::rcvcopy_front_kernel<8>, fgrid, block, 0, st, buf, win, wplan, wsum, n, arena);
+    else
+        hipLaunchKernelGGL(mg::rcvcopy_front_kernel<32>, fgrid, block, 0, st, buf, win, wplan, wsum, n, arena);
+    hipLaunchKernelGGL(mg::rcvcopy_ordered_kernel, grid, block, 0, st, buf, win, wplan, wsum, n, max_id, d_seg_sid,
+                       d_seg_start, d_nseg, d_seg_stop, arena);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
 // ---- device flow table ----------------------------------------

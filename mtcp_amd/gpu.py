@@ -376,6 +376,27 @@ class Context:
                                      state.ctypes.data, place.ctypes.data, seg_stop.ctypes.data), "mtcp_gpu_rcvwalk")
         return place, seg_stop[:m]
 
+    # -- the payload copy behind the walk (tcp_ring_buffer.c:304-319; mtcp_gpu_rcvcopy.h) --
+    @staticmethod
+    def rcvcopy_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_rcvcopy_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_rcvcopy_work_bytes(n, max_id)
+
+    def rcvcopy_dev(self, buf, desc, off_shift: int, res, place, n: int, max_id: int, idx, seg_sid, seg_start, nseg,
+                    seg_stop, rbuf, arena, cstat, work, stream=None) -> None:
+        """buf, desc, off_shift: the chunk as rx_chunk_dev saw it; res: n x 40 B
+        records; place, seg_stop: as rcvwalk_dev wrote them; idx, seg_sid,
+        seg_start, nseg: as group_dev wrote them; rbuf: (max_id + 1) x 32 B
+        (RCV_BUF_DTYPE), updated; arena: the receive buffers' bytes, written;
+        cstat: n x u8; work: at least rcvcopy_work_bytes(n, max_id) bytes."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_rcvcopy_dev(self._h, _dptr(buf), buf.numel() * buf.element_size(), _dptr(desc),
+                                             off_shift, _dptr(res), _dptr(place), n, max_id, _dptr(idx),
+                                             _dptr(seg_sid), _dptr(seg_start), _dptr(nseg), _dptr(seg_stop),
+                                             _dptr(rbuf), _dptr(arena), arena.numel() * arena.element_size(),
+                                             _dptr(cstat), _dptr(work), work.numel() * work.element_size(), st),
+                  "mtcp_gpu_rcvcopy_dev")
+
     # -- tx frames from segment records (tcp_out.c:135-354; mtcp_gpu_txbuild.h) --
     def tx_build_dev(self, seg, n: int, payload, links, buf, desc, off_shift: int, status,
                      max_mss: int = 0, flags: int = 0, stream=None) -> None:
