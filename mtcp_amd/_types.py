@@ -128,6 +128,29 @@ RCV_VERDICTS = ("NONE", "DEFER_STATE", "DEFER_BAD_STATE", "DEFER_FLAGS", "DEFER_
                 "PUT_NO_ROOM", "PUT_STORED")
 RCV_MAX_FRAGS, RCV_MAX_SIZE, RCV_ST_ESTABLISHED = 4, 1 << 30, 4
 
+# include/mtcp_gpu_ackwalk.h: struct mtcp_gpu_ack_state (one stream's send
+# state, 128 B: d_snd[max_id + 1] indexed by stream id; bytes 88-127 are the
+# caller's) and struct mtcp_gpu_ack_rec (one packet's ACK record)
+ACK_STATE_DTYPE = np.dtype([
+    ("snd_nxt", "<u4"), ("snd_una", "<u4"), ("snd_wnd", "<u4"), ("peer_wnd", "<u4"), ("snd_wl1", "<u4"),
+    ("snd_wl2", "<u4"), ("last_ack_seq", "<u4"), ("cwnd", "<u4"), ("ssthresh", "<u4"), ("rto", "<u4"),
+    ("ts_rto", "<u4"), ("srtt", "<u4"), ("mdev", "<u4"), ("mdev_max", "<u4"), ("rttvar", "<u4"), ("rtt_seq", "<u4"),
+    ("sb_head_seq", "<u4"), ("sb_len", "<u4"), ("sb_size", "<u4"), ("mss", "<u2"), ("eff_mss", "<u2"),
+    ("tcp_state", "u1"), ("saw_timestamp", "u1"), ("wscale_peer", "u1"), ("dup_acks", "u1"), ("nrtx", "u1"),
+    ("on_rto", "u1"), ("has_sndbuf", "u1"), ("rsvd", "u1"), ("user", "u1", (40,))])
+ACK_REC_DTYPE = np.dtype([("rmlen", "<u4"), ("snd_nxt", "<u4"), ("cwnd", "<u4"), ("flags", "<u2"), ("verdict", "u1"),
+                          ("dup_acks", "u1")])
+assert ACK_STATE_DTYPE.itemsize == 128 and ACK_REC_DTYPE.itemsize == 16
+assert [ACK_STATE_DTYPE.fields[f][1] for f in ACK_STATE_DTYPE.names] == \
+    list(range(0, 76, 4)) + [76, 78, 80, 81, 82, 83, 84, 85, 86, 87, 88]
+(ACK_WND_UPDATE, ACK_WRITE_EVENT_WND, ACK_DUP, ACK_FAST_RTX, ACK_SND_NXT_RECOVERED, ACK_SEND_LIST_REMOVE,
+ ACK_WRITE_EVENT_ROOM, ACK_RTO_REMOVE, ACK_RTO_ADD) = (1 << k for k in range(9))
+ACK_FLAGS = ("WND_UPDATE", "WRITE_EVENT_WND", "DUP", "FAST_RTX", "SND_NXT_RECOVERED", "SEND_LIST_REMOVE",
+             "WRITE_EVENT_ROOM", "RTO_REMOVE", "RTO_ADD")
+ACK_VERDICTS = ("NONE", "DEFER_RCV", "DEFER_STATE", "DEFER_BAD_STATE", "DEFER_FLAGS", "DEFER_ARITH", "DEFER_BEHIND",
+                "NOT_VALID", "NO_ACK_FLAG", "NO_SNDBUF", "ACK_BEYOND", "ACK_OLD", "ACK_NEW")
+ACK_MAX_SIZE, ACK_ST_ESTABLISHED, ACK_MAX_RTX = 1 << 30, 4, 16
+
 # include/mtcp_gpu_rcvcopy.h: struct mtcp_gpu_rcv_buf (one stream's receive
 # buffer in the arena: what RBPut's byte work reads and writes of it,
 # tcp_ring_buffer.c:304-319) and the status bytes of d_cstat

@@ -19,6 +19,7 @@
 #include "../../include/mtcp_gpu_flowtab.h"
 #include "../../include/mtcp_gpu_group.h"
 #include "../../include/mtcp_gpu_rcvwalk.h"
+#include "../../include/mtcp_gpu_ackwalk.h"
 #include "../../include/mtcp_gpu_rcvcopy.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
@@ -33,6 +34,7 @@
 #include "host_copy.hpp"
 #include "park.hpp"
 #include "rcvwalk_kernels.hpp"
+#include "ackwalk_kernels.hpp"
 #include "rcvcopy_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
@@ -1521,6 +1523,120 @@ int mtcp_gpu_rcvwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_g
     hc.down(state, d_state, sbytes);
     hc.down(place, at(place_off), pbytes);
     hc.down(seg_stop, at(stop_off), mbytes);
+    return hc.finish();
+}
+
+// ---- the per-stream ProcessACK walk -----------------------------
+static_assert(sizeof(mtcp_gpu_ack_state) == 128 && sizeof(mtcp_gpu_ack_rec) == 16, "mtcp_gpu_ackwalk.h layouts");
+static_assert(offsetof(mtcp_gpu_ack_state, sb_head_seq) == 64 && offsetof(mtcp_gpu_ack_state, mss) == 76 &&
+              offsetof(mtcp_gpu_ack_state, tcp_state) == 80 && offsetof(mtcp_gpu_ack_state, nrtx) == 84 &&
+              offsetof(mtcp_gpu_ack_state, user) == 88 && offsetof(mtcp_gpu_ack_rec, flags) == 12 &&
+              offsetof(mtcp_gpu_ack_rec, verdict) == 14,
+              "ackwalk_kernels.hpp reads and writes the records as 16 B pieces");
+static_assert(offsetof(mtcp_gpu_result, ack_seq) == 16 && offsetof(mtcp_gpu_result, window) == 20,
+              "ackwalk_gather_kernel's loads of a record");
+
+uint32_t mtcp_gpu_ackwalk_short_len(void) { return mg::kAckShortLen; }
+
+uint64_t mtcp_gpu_ackwalk_work_bytes(uint32_t n, uint32_t max_id) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return 0;
+    return mg::ack_work(n).bytes;
+}
+
+int mtcp_gpu_ackwalk_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, const mtcp_gpu_tcpopt *d_opt,
+                         const mtcp_gpu_rcv_place *d_place, uint32_t n, uint32_t max_id, const uint32_t *d_idx,
+                         const uint32_t *d_seg_sid, const uint32_t *d_seg_start, const uint32_t *d_nseg,
+                         uint32_t cur_ts, mtcp_gpu_ack_state *d_snd, mtcp_gpu_ack_rec *d_ack, uint32_t *d_ack_stop,
+                         void *d_work, uint64_t work_bytes, void *stream) {
+    if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
+        (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        (n && (!d_res || !d_place || !d_idx || !d_seg_sid || !d_seg_start || !d_nseg || !d_snd || !d_ack ||
+               !d_ack_stop || !d_work)) ||
+        ((uintptr_t)d_res & 7) || ((uintptr_t)d_opt & 15) || ((uintptr_t)d_place & 15) || ((uintptr_t)d_idx & 3) ||
+        ((uintptr_t)d_seg_sid & 3) || ((uintptr_t)d_seg_start & 3) || ((uintptr_t)d_nseg & 3) ||
+        ((uintptr_t)d_snd & 127) || ((uintptr_t)d_ack & 15) || ((uintptr_t)d_ack_stop & 3) || ((uintptr_t)d_work & 15))
+        return MTCP_GPU_EINVAL;
+    const mg::AckWork w = mg::ack_work(n);
+    if (n && work_bytes < w.bytes) return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const dim3 block(mg::kBlock), grid((n + mg::kBlock - 1) / mg::kBlock);
+    uint4 *win = reinterpret_cast<uint4 *>(static_cast<uint8_t *>(d_work) + w.in_off);
+    hipLaunchKernelGGL(mg::ackwalk_gather_kernel, grid, block, 0, st, reinterpret_cast<const uint8_t *>(d_res),
+                       reinterpret_cast<const uint4 *>(d_opt), reinterpret_cast<const uint4 *>(d_place), d_idx, n, win,
+                       reinterpret_cast<uint4 *>(d_ack));
+    hipLaunchKernelGGL((mg::ackwalk_walk_kernel<mg::kAckShortLen, mg::kAckWaveMax>), grid, block, 0, st, win, d_idx, n, max_id,
+                       d_seg_sid, d_seg_start, d_nseg, cur_ts, reinterpret_cast<uint4 *>(d_snd),
+                       reinterpret_cast<uint4 *>(d_ack), d_ack_stop);
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+// Stage 0's chunk buffer as in mtcp_gpu_rcvwalk: the inputs (res, opt, place,
+// idx, seg_sid[m], seg_start[m + 1], nseg, each padded to 16 B), then in one
+// piece what comes back (snd[max_id + 1] at a 128 B boundary, ack[n],
+// ack_stop[n]), then the workspace.
+int mtcp_gpu_ackwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_gpu_tcpopt *opt,
+                     const mtcp_gpu_rcv_place *place, uint32_t n, uint32_t max_id, const uint32_t *idx,
+                     const uint32_t *seg_sid, const uint32_t *seg_start, const uint32_t *nseg, uint32_t cur_ts,
+                     mtcp_gpu_ack_state *snd, mtcp_gpu_ack_rec *ack, uint32_t *ack_stop) {
+    if (!ctx || n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID ||
+        (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        (n && (!res || !place || !idx || !seg_sid || !seg_start || !nseg || !snd || !ack || !ack_stop)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const uint32_t m = std::min(nseg[0], n);
+    const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_result), obytes = opt ? (uint64_t)n * sizeof(mtcp_gpu_tcpopt) : 0;
+    const uint64_t pbytes = (uint64_t)n * sizeof(mtcp_gpu_rcv_place);
+    const uint64_t ibytes = (uint64_t)n * sizeof(uint32_t), mbytes = (uint64_t)m * sizeof(uint32_t);
+    const uint64_t sbytes = ((uint64_t)max_id + 1) * sizeof(mtcp_gpu_ack_state);
+    const uint64_t abytes = (uint64_t)n * sizeof(mtcp_gpu_ack_rec);
+    const uint64_t res_off = 0, opt_off = res_off + pad16(rbytes), place_off = opt_off + pad16(obytes);
+    const uint64_t idx_off = place_off + pbytes, sid_off = idx_off + pad16(ibytes), start_off = sid_off + pad16(mbytes);
+    const uint64_t nseg_off = start_off + pad16(mbytes + 4);
+    const uint64_t snd_off = (nseg_off + 16 + 127) & ~127ull, ack_off = snd_off + sbytes;
+    const uint64_t stop_off = ack_off + abytes, back_bytes = sbytes + abytes + ibytes;
+    const uint64_t work_off = pad16(stop_off + ibytes), wbytes = mg::ack_work(n).bytes;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, work_off + wbytes, 0, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, snd_off + sbytes, back_bytes, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    auto at = [&](uint64_t off) { return s.d_buf + off; };
+    mtcp_gpu_ack_state *d_snd = reinterpret_cast<mtcp_gpu_ack_state *>(at(snd_off));
+    Call hc(s, dl, {ctx, dl});
+    hc.up(at(res_off), res, rbytes);
+    if (opt) hc.up(at(opt_off), opt, obytes);
+    hc.up(at(place_off), place, pbytes);
+    hc.up(at(idx_off), idx, ibytes);
+    hc.up(at(sid_off), seg_sid, mbytes);
+    hc.up(at(start_off), seg_start, mbytes + 4);
+    hc.up(at(nseg_off), &m, sizeof(uint32_t));
+    hc.up(d_snd, snd, sbytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_ackwalk_dev(ctx, reinterpret_cast<const mtcp_gpu_result *>(at(res_off)),
+                                     opt ? reinterpret_cast<const mtcp_gpu_tcpopt *>(at(opt_off)) : nullptr,
+                                     reinterpret_cast<const mtcp_gpu_rcv_place *>(at(place_off)), n, max_id,
+                                     reinterpret_cast<const uint32_t *>(at(idx_off)),
+                                     reinterpret_cast<const uint32_t *>(at(sid_off)),
+                                     reinterpret_cast<const uint32_t *>(at(start_off)),
+                                     reinterpret_cast<const uint32_t *>(at(nseg_off)), cur_ts, d_snd,
+                                     reinterpret_cast<mtcp_gpu_ack_rec *>(at(ack_off)),
+                                     reinterpret_cast<uint32_t *>(at(stop_off)), at(work_off), wbytes, s.stream));
+    if (hc.bounded()) {
+        const uint8_t *h = hc.down_pinned(d_snd, back_bytes);
+        if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+        memcpy(snd, h, sbytes);
+        memcpy(ack, h + sbytes, abytes);
+        memcpy(ack_stop, h + sbytes + abytes, mbytes);
+        return rc;
+    }
+    hc.down(snd, d_snd, sbytes);
+    hc.down(ack, at(ack_off), abytes);
+    hc.down(ack_stop, at(stop_off), mbytes);
     return hc.finish();
 }
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -375,6 +375,52 @@ class Context:
                                      idx.ctypes.data, seg_sid.ctypes.data, seg_start.ctypes.data, nseg.ctypes.data,
                                      state.ctypes.data, place.ctypes.data, seg_stop.ctypes.data), "mtcp_gpu_rcvwalk")
         return place, seg_stop[:m]
+
+    # -- the per-stream ProcessACK walk (tcp_in.c:302-531; mtcp_gpu_ackwalk.h) --
+    @staticmethod
+    def ackwalk_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_ackwalk_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_ackwalk_work_bytes(n, max_id)
+
+    @staticmethod
+    def ackwalk_short_len() -> int:
+        return lib().mtcp_gpu_ackwalk_short_len()
+
+    def ackwalk_dev(self, res, opt, place, n: int, max_id: int, idx, seg_sid, seg_start, nseg, cur_ts: int, snd, ack,
+                    ack_stop, work, stream=None) -> None:
+        """res: n x 40 B records; opt: n x 16 B option records or None; place:
+        n x 16 B as rcvwalk_dev wrote them; idx, seg_sid, seg_start, nseg: as
+        group_dev wrote them; snd: (max_id + 1) x 128 B (ACK_STATE_DTYPE),
+        updated; ack: n x 16 B (ACK_REC_DTYPE); ack_stop: n x u32; work: at
+        least ackwalk_work_bytes(n, max_id) bytes."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_ackwalk_dev(self._h, _dptr(res), None if opt is None else _dptr(opt), _dptr(place), n,
+                                             max_id, _dptr(idx), _dptr(seg_sid), _dptr(seg_start), _dptr(nseg),
+                                             cur_ts & 0xFFFFFFFF, _dptr(snd), _dptr(ack), _dptr(ack_stop), _dptr(work),
+                                             work.numel() * work.element_size(), st), "mtcp_gpu_ackwalk_dev")
+
+    def ackwalk(self, res: np.ndarray, opt, place: np.ndarray, max_id: int, idx: np.ndarray, seg_sid: np.ndarray,
+                seg_start: np.ndarray, cur_ts: int, snd: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """mtcp_gpu_ackwalk over the arrays group() and rcvwalk() returned:
+        `snd` ((max_id + 1) x ACK_STATE_DTYPE) is updated in place; returns
+        (ack, ack_stop), ack_stop cut to the table's m entries."""
+        res = np.ascontiguousarray(res, dtype=RESULT_DTYPE)
+        if opt is not None:
+            opt = np.ascontiguousarray(opt, dtype=TCPOPT_DTYPE)
+        place = np.ascontiguousarray(place, dtype=RCV_PLACE_DTYPE)
+        n, m = len(res), len(seg_sid)
+        if snd.dtype != ACK_STATE_DTYPE or not snd.flags.c_contiguous or len(snd) != max_id + 1:
+            raise ValueError("snd: (max_id + 1) contiguous ACK_STATE_DTYPE records")
+        if len(place) != n:
+            raise ValueError("place: one record per packet")
+        idx, seg_sid = np.ascontiguousarray(idx, dtype=np.uint32), np.ascontiguousarray(seg_sid, dtype=np.uint32)
+        seg_start, nseg = np.ascontiguousarray(seg_start, dtype=np.uint32), np.array([m], dtype=np.uint32)
+        ack, ack_stop = np.zeros(n, dtype=ACK_REC_DTYPE), np.zeros(max(m, 1), dtype=np.uint32)
+        check(lib().mtcp_gpu_ackwalk(self._h, res.ctypes.data, None if opt is None else opt.ctypes.data,
+                                     place.ctypes.data, n, max_id, idx.ctypes.data, seg_sid.ctypes.data,
+                                     seg_start.ctypes.data, nseg.ctypes.data, cur_ts & 0xFFFFFFFF, snd.ctypes.data,
+                                     ack.ctypes.data, ack_stop.ctypes.data), "mtcp_gpu_ackwalk")
+        return ack, ack_stop[:m]
 
     # -- the payload copy behind the walk (tcp_ring_buffer.c:304-319; mtcp_gpu_rcvcopy.h) --
     @staticmethod
