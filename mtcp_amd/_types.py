@@ -151,6 +151,22 @@ ACK_VERDICTS = ("NONE", "DEFER_RCV", "DEFER_STATE", "DEFER_BAD_STATE", "DEFER_FL
                 "NOT_VALID", "NO_ACK_FLAG", "NO_SNDBUF", "ACK_BEYOND", "ACK_OLD", "ACK_NEW")
 ACK_MAX_SIZE, ACK_ST_ESTABLISHED, ACK_MAX_RTX = 1 << 30, 4, 16
 
+# include/mtcp_gpu_ackgen.h: struct mtcp_gpu_ackgen_state (what WriteTCPACKList
+# and SendTCPPacket read of one stream beyond the walks' states, 32 B:
+# d_tx[max_id + 1] indexed by stream id) and struct mtcp_gpu_ackgen_res (one
+# segment's result)
+ACKGEN_STATE_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
+                               ("ip_id", "<u2"), ("ack_cnt", "u1"), ("is_wack", "u1"), ("wscale_mine", "u1"),
+                               ("link", "u1"), ("has_rcvbuf", "u1"), ("need_wnd_adv", "u1"),
+                               ("ts_lastack_sent", "<u4"), ("rsvd", "u1", (8,))])
+ACKGEN_RES_DTYPE = np.dtype([("first_seg", "<u4"), ("n_ack", "u1"), ("wack", "u1"), ("status", "u1"), ("flags", "u1"),
+                             ("ack", "<u4"), ("window", "<u2"), ("rsvd", "<u2")])
+assert ACKGEN_STATE_DTYPE.itemsize == 32 and ACKGEN_RES_DTYPE.itemsize == 16
+assert [ACKGEN_STATE_DTYPE.fields[f][1] for f in ACKGEN_STATE_DTYPE.names] == \
+    [0, 4, 8, 10, 12, 14, 15, 16, 17, 18, 19, 20, 24]
+ACKGEN_STATUS = ("NONE", "BAD", "DEFERRED", "IDLE", "NOT_TO_ACK", "SENT", "NO_ROOM")
+ACKGEN_ON_LIST, ACKGEN_NEED_WND_ADV, ACKGEN_FRAME_LEN = 0x1, 0x2, 66
+
 # include/mtcp_gpu_rcvcopy.h: struct mtcp_gpu_rcv_buf (one stream's receive
 # buffer in the arena: what RBPut's byte work reads and writes of it,
 # tcp_ring_buffer.c:304-319) and the status bytes of d_cstat

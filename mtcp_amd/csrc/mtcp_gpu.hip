@@ -20,6 +20,7 @@
 #include "../../include/mtcp_gpu_group.h"
 #include "../../include/mtcp_gpu_rcvwalk.h"
 #include "../../include/mtcp_gpu_ackwalk.h"
+#include "../../include/mtcp_gpu_ackgen.h"
 #include "../../include/mtcp_gpu_rcvcopy.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
@@ -35,6 +36,7 @@
 #include "park.hpp"
 #include "rcvwalk_kernels.hpp"
 #include "ackwalk_kernels.hpp"
+#include "ackgen_kernels.hpp"
 #include "rcvcopy_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
@@ -2272,6 +2274,206 @@ int mtcp_gpu_tx_send(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *burst, uint32_t
     memcpy(status, hs, seg_cap);
     if (rbytes) memcpy(res, hb + (res_off - desc_off), rbytes);
     memcpy(total, hb + (tot_off - desc_off), 16);
+    return MTCP_GPU_OK;
+}
+
+// ---- pure-ACK tx segments from a walked rx batch ----------------
+static_assert(sizeof(mtcp_gpu_ackgen_state) == 32 && offsetof(mtcp_gpu_ackgen_state, ip_id) == 12 &&
+              offsetof(mtcp_gpu_ackgen_state, wscale_mine) == 16 && offsetof(mtcp_gpu_ackgen_state, ts_lastack_sent) == 20 &&
+              offsetof(mtcp_gpu_ackgen_state, rsvd) == 24 && sizeof(mtcp_gpu_ackgen_res) == 16 &&
+              offsetof(mtcp_gpu_ackgen_res, status) == 6 && offsetof(mtcp_gpu_ackgen_res, window) == 12,
+              "ackgen_step.hpp reads and writes the records as dwords");
+static_assert(offsetof(mtcp_gpu_rcv_place, put_len) == 12 && offsetof(mtcp_gpu_rcv_place, verdict) == 14 &&
+              offsetof(mtcp_gpu_rcv_state, ts_recent) == 20 && offsetof(mtcp_gpu_rcv_state, tcp_state) == 28 &&
+              offsetof(mtcp_gpu_ack_state, snd_nxt) == 0 && sizeof(mtcp_gpu_tx_seg) == 48 &&
+              offsetof(mtcp_gpu_tx_seg, window) == 36 && offsetof(mtcp_gpu_tx_seg, flags) == 44,
+              "ackgen_plan_kernel's loads, ackgen_record's dwords");
+
+namespace {
+
+bool ackgen_geom_ok(uint32_t n, uint32_t max_id, uint32_t n_links, uint64_t buf_off, uint32_t off_shift,
+                    uint32_t slot_bytes, uint32_t seg_cap) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return false;
+    if (slot_bytes && slot_bytes < MTCP_GPU_ACKGEN_FRAME_LEN) return false;
+    return txseg_geom_ok(0, n_links, buf_off, off_shift, slot_bytes, seg_cap);
+}
+
+bool ackgen_dev_args_ok(const mtcp_gpu_ctx *ctx, const void *d_place, uint32_t n, uint32_t max_id, const void *d_idx,
+                        const void *d_seg_sid, const void *d_seg_start, const void *d_nseg, const void *d_seg_stop,
+                        const void *d_ack_stop, const void *d_state, const void *d_snd, const void *d_tx,
+                        uint32_t n_links, uint64_t buf_off, uint32_t off_shift, uint32_t slot_bytes,
+                        const void *d_seg, const void *d_desc, uint32_t seg_cap, const void *d_ares,
+                        const void *d_total, const void *d_work, uint64_t work_bytes) {
+    if (!ctx || (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        !ackgen_geom_ok(n, max_id, n_links, buf_off, off_shift, slot_bytes, seg_cap))
+        return false;
+    if (!d_seg || !d_desc || !d_total ||
+        (n && (!d_place || !d_idx || !d_seg_sid || !d_seg_start || !d_nseg || !d_seg_stop || !d_state || !d_snd ||
+               !d_tx || !d_ares || !d_work)))
+        return false;
+    if (((uintptr_t)d_place & 15) || ((uintptr_t)d_idx & 3) || ((uintptr_t)d_seg_sid & 3) ||
+        ((uintptr_t)d_seg_start & 3) || ((uintptr_t)d_nseg & 3) || ((uintptr_t)d_seg_stop & 3) ||
+        ((uintptr_t)d_ack_stop & 3) || ((uintptr_t)d_state & 63) || ((uintptr_t)d_snd & 127) ||
+        ((uintptr_t)d_tx & 31) || ((uintptr_t)d_seg & 7) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_ares & 15) ||
+        ((uintptr_t)d_total & 7) || ((uintptr_t)d_work & 15))
+        return false;
+    return !n || work_bytes >= mg::ackgen_work(n).bytes;
+}
+
+}  // namespace
+
+uint32_t mtcp_gpu_ackgen_lane_len(void) { return mg::kAckgenLaneMax; }
+
+uint64_t mtcp_gpu_ackgen_work_bytes(uint32_t n, uint32_t max_id) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return 0;
+    return mg::ackgen_work(n).bytes;
+}
+
+int mtcp_gpu_ackgen_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcv_place *d_place, uint32_t n, uint32_t max_id,
+                        const uint32_t *d_idx, const uint32_t *d_seg_sid, const uint32_t *d_seg_start,
+                        const uint32_t *d_nseg, const uint32_t *d_seg_stop, const uint32_t *d_ack_stop,
+                        const mtcp_gpu_rcv_state *d_state, const mtcp_gpu_ack_state *d_snd, uint32_t cur_ts,
+                        mtcp_gpu_ackgen_state *d_tx, uint32_t n_links, uint64_t buf_off, uint64_t buf_len,
+                        uint32_t off_shift, uint32_t slot_bytes, mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc,
+                        uint32_t seg_cap, mtcp_gpu_ackgen_res *d_ares, uint64_t *d_total, void *d_work,
+                        uint64_t work_bytes, void *stream) {
+    if (!ackgen_dev_args_ok(ctx, d_place, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop, d_ack_stop,
+                            d_state, d_snd, d_tx, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc, seg_cap,
+                            d_ares, d_total, d_work, work_bytes))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    mg::AckGenParams P{};
+    P.buf_off = buf_off;
+    P.n = n, P.max_id = max_id, P.n_links = n_links, P.cur_ts = cur_ts, P.off_shift = off_shift;
+    P.slot = mg::ackgen_slot(off_shift, slot_bytes);
+    P.seg_cap = seg_cap;
+    P.room = mg::ackgen_room(buf_off, buf_len, off_shift, P.slot, seg_cap);
+    const mg::AckGenWork w = mg::ackgen_work(n);
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    mg::v4u *plan = reinterpret_cast<mg::v4u *>(work + w.plan_off);
+    uint32_t *local = reinterpret_cast<uint32_t *>(work + w.local_off);
+    uint32_t *part_c = reinterpret_cast<uint32_t *>(work + w.pc_off);
+    uint64_t *part_b = reinterpret_cast<uint64_t *>(work + w.pb_off);
+    unsigned long long *tot_b = reinterpret_cast<unsigned long long *>(work + w.tot_off);
+    uint32_t *tot_c = reinterpret_cast<uint32_t *>(work + w.tot_off + 8);
+    const dim3 block(mg::kBlock);
+    if (n) {
+        hipLaunchKernelGGL(mg::ackgen_plan_kernel<mg::kAckgenLaneMax>, dim3(w.nwg), block, 0, st, reinterpret_cast<const uint8_t *>(d_place),
+                           d_idx, P, d_seg_sid, d_seg_start, d_nseg, d_seg_stop, d_ack_stop,
+                           reinterpret_cast<const uint8_t *>(d_state), reinterpret_cast<const uint8_t *>(d_snd),
+                           reinterpret_cast<const uint8_t *>(d_tx), plan, local, part_c, part_b);
+        hipLaunchKernelGGL(mg::txseg_scan_kernel, dim3(1), block, 0, st, part_c, part_b, w.nwg, seg_cap, tot_c, tot_b);
+    }
+    const uint32_t lanes = std::max(seg_cap, n);
+    hipLaunchKernelGGL(mg::ackgen_emit_kernel, dim3((lanes + mg::kBlock - 1) / mg::kBlock), block, 0, st, plan, local,
+                       part_c, tot_c, d_nseg, w.nwg, P, d_seg_sid, reinterpret_cast<uint8_t *>(d_tx), d_seg, d_desc,
+                       d_ares, d_total);
+    ctx->last_kernel = "ackgen_emit_kernel";
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+int mtcp_gpu_ack_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcv_place *d_place, uint32_t n, uint32_t max_id,
+                          const uint32_t *d_idx, const uint32_t *d_seg_sid, const uint32_t *d_seg_start,
+                          const uint32_t *d_nseg, const uint32_t *d_seg_stop, const uint32_t *d_ack_stop,
+                          const mtcp_gpu_rcv_state *d_state, const mtcp_gpu_ack_state *d_snd, uint32_t cur_ts,
+                          mtcp_gpu_ackgen_state *d_tx, const mtcp_gpu_tx_link *d_links, uint32_t n_links,
+                          void *d_buf, uint64_t buf_off, uint64_t buf_len, uint32_t off_shift,
+                          uint32_t slot_bytes, uint32_t flags, mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc,
+                          uint32_t seg_cap, mtcp_gpu_ackgen_res *d_ares, uint64_t *d_total, uint8_t *d_status,
+                          void *d_work, uint64_t work_bytes, void *stream) {
+    // both calls' checks before either launches; the builder's payload is the
+    // workspace pointer with no bytes (never dereferenced for payload_len == 0)
+    if (!ackgen_dev_args_ok(ctx, d_place, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop, d_ack_stop,
+                            d_state, d_snd, d_tx, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc, seg_cap,
+                            d_ares, d_total, d_work, work_bytes) ||
+        !txbuild_args_ok(ctx, seg_cap, d_seg, d_work, 0, d_links, n_links, d_buf, buf_len, d_desc, off_shift, flags,
+                         d_status) ||
+        ((uintptr_t)d_links & 3))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    const int rc = mtcp_gpu_ackgen_dev(ctx, d_place, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop,
+                                       d_ack_stop, d_state, d_snd, cur_ts, d_tx, n_links, buf_off, buf_len, off_shift,
+                                       slot_bytes, d_seg, d_desc, seg_cap, d_ares, d_total, d_work, work_bytes,
+                                       stream);
+    if (rc != MTCP_GPU_OK) return rc;
+    return mtcp_gpu_tx_build_dev(ctx, d_seg, seg_cap, d_work, 0, d_links, n_links, d_buf, buf_len, d_desc, off_shift,
+                                 0, flags, d_status, stream);
+}
+
+// Stage 0's chunk buffer: the inputs (place, idx, seg_sid[m], seg_start[m + 1],
+// nseg, seg_stop[m], ack_stop[m], state and snd at their alignments), then in
+// one piece what comes back (tx[max_id + 1], seg[seg_cap], desc[seg_cap],
+// ares[n], total[2]), then the workspace.
+int mtcp_gpu_ackgen(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcv_place *place, uint32_t n, uint32_t max_id,
+                    const uint32_t *idx, const uint32_t *seg_sid, const uint32_t *seg_start, const uint32_t *nseg,
+                    const uint32_t *seg_stop, const uint32_t *ack_stop, const mtcp_gpu_rcv_state *state,
+                    const mtcp_gpu_ack_state *snd, uint32_t cur_ts, mtcp_gpu_ackgen_state *tx, uint32_t n_links,
+                    uint64_t buf_off, uint64_t buf_len, uint32_t off_shift, uint32_t slot_bytes,
+                    mtcp_gpu_tx_seg *seg, mtcp_gpu_desc *desc, uint32_t seg_cap, mtcp_gpu_ackgen_res *ares,
+                    uint64_t total[2]) {
+    if (!ctx || (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        !ackgen_geom_ok(n, max_id, n_links, buf_off, off_shift, slot_bytes, seg_cap) || !seg || !desc || !total ||
+        (n && (!place || !idx || !seg_sid || !seg_start || !nseg || !seg_stop || !state || !snd || !tx || !ares)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const uint32_t m = n ? std::min(nseg[0], n) : 0u;
+    const uint64_t ids = n ? (uint64_t)max_id + 1 : 0;
+    const uint64_t pbytes = (uint64_t)n * sizeof(mtcp_gpu_rcv_place), ibytes = (uint64_t)n * sizeof(uint32_t);
+    const uint64_t mbytes = (uint64_t)m * sizeof(uint32_t);
+    const uint64_t stbytes = ids * sizeof(mtcp_gpu_rcv_state), snbytes = ids * sizeof(mtcp_gpu_ack_state);
+    const uint64_t txbytes = ids * sizeof(mtcp_gpu_ackgen_state);
+    const uint64_t sgbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_tx_seg), dbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_desc);
+    const uint64_t abytes = (uint64_t)n * sizeof(mtcp_gpu_ackgen_res);
+    const uint64_t place_off = 0, idx_off = place_off + pbytes, sid_off = idx_off + pad16(ibytes);
+    const uint64_t start_off = sid_off + pad16(mbytes), nseg_off = start_off + pad16(mbytes + 4);
+    const uint64_t stop_off = nseg_off + 16, astop_off = stop_off + pad16(mbytes);
+    const uint64_t snd_off = (astop_off + pad16(mbytes) + 127) & ~127ull, state_off = snd_off + snbytes;
+    const uint64_t tx_off = state_off + stbytes;                              // 32 B aligned: both are multiples of 64
+    const uint64_t seg_off = tx_off + txbytes, desc_off = seg_off + sgbytes, ares_off = desc_off + pad16(dbytes);
+    const uint64_t tot_off = ares_off + abytes, back_bytes = tot_off + 16 - tx_off;
+    const uint64_t work_off = tot_off + 16, wbytes = mg::ackgen_work(n).bytes;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, grown(work_off + wbytes, s.buf_cap), 0, dl);
+    if (rc == MTCP_GPU_OK)
+        rc = stage_host(ctx, s, dl.bounded ? grown(tx_off + txbytes, s.h_in_cap) : 0, grown(back_bytes, s.h_out_cap), dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    auto at = [&](uint64_t off) { return s.d_buf + off; };
+    auto u32p = [&](uint64_t off) { return reinterpret_cast<const uint32_t *>(at(off)); };
+    Call hc(s, dl, {ctx, dl});
+    if (n) {
+        hc.up(at(place_off), place, pbytes);
+        hc.up(at(idx_off), idx, ibytes);
+        hc.up(at(sid_off), seg_sid, mbytes);
+        hc.up(at(start_off), seg_start, mbytes + 4);
+        hc.up(at(nseg_off), &m, sizeof(uint32_t));
+        hc.up(at(stop_off), seg_stop, mbytes);
+        if (ack_stop) hc.up(at(astop_off), ack_stop, mbytes);
+        hc.up(at(snd_off), snd, snbytes);
+        hc.up(at(state_off), state, stbytes);
+        hc.up(at(tx_off), tx, txbytes);
+    }
+    if (hc.ok())
+        hc.note(mtcp_gpu_ackgen_dev(ctx, reinterpret_cast<const mtcp_gpu_rcv_place *>(at(place_off)), n, max_id,
+                                    u32p(idx_off), u32p(sid_off), u32p(start_off), u32p(nseg_off), u32p(stop_off),
+                                    ack_stop ? u32p(astop_off) : nullptr,
+                                    reinterpret_cast<const mtcp_gpu_rcv_state *>(at(state_off)),
+                                    reinterpret_cast<const mtcp_gpu_ack_state *>(at(snd_off)), cur_ts,
+                                    reinterpret_cast<mtcp_gpu_ackgen_state *>(at(tx_off)), n_links, buf_off, buf_len,
+                                    off_shift, slot_bytes, reinterpret_cast<mtcp_gpu_tx_seg *>(at(seg_off)),
+                                    reinterpret_cast<mtcp_gpu_desc *>(at(desc_off)), seg_cap,
+                                    reinterpret_cast<mtcp_gpu_ackgen_res *>(at(ares_off)),
+                                    reinterpret_cast<uint64_t *>(at(tot_off)), at(work_off), wbytes, s.stream));
+    const uint8_t *h = hc.down_pinned(at(tx_off), back_bytes);
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+    if (txbytes) memcpy(tx, h, txbytes);
+    memcpy(seg, h + (seg_off - tx_off), sgbytes);
+    memcpy(desc, h + (desc_off - tx_off), dbytes);
+    if (m) memcpy(ares, h + (ares_off - tx_off), (uint64_t)m * sizeof(mtcp_gpu_ackgen_res));
+    memcpy(total, h + (tot_off - tx_off), 16);
     return MTCP_GPU_OK;
 }
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -421,6 +421,79 @@ class Context:
                                      seg_start.ctypes.data, nseg.ctypes.data, cur_ts & 0xFFFFFFFF, snd.ctypes.data,
                                      ack.ctypes.data, ack_stop.ctypes.data), "mtcp_gpu_ackwalk")
         return ack, ack_stop[:m]
+
+    # -- pure-ACK tx segments from a walked batch (tcp_out.c:911-935, :697-761, :220-354; mtcp_gpu_ackgen.h) --
+    @staticmethod
+    def ackgen_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_ackgen_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_ackgen_work_bytes(n, max_id)
+
+    @staticmethod
+    def ackgen_lane_len() -> int:
+        return lib().mtcp_gpu_ackgen_lane_len()
+
+    def ackgen_dev(self, place, n: int, max_id: int, idx, seg_sid, seg_start, nseg, seg_stop, ack_stop, state, snd,
+                   cur_ts: int, tx, n_links: int, buf_off: int, buf_len: int, off_shift: int, slot_bytes: int, seg,
+                   desc, seg_cap: int, ares, total, work, stream=None) -> None:
+        """place, seg_stop: as rcvwalk_dev wrote them; ack_stop: as ackwalk_dev
+        wrote it, or None; idx, seg_sid, seg_start, nseg: as group_dev wrote
+        them; state, snd: the walks' (max_id + 1) records; tx: (max_id + 1) x
+        32 B (ACKGEN_STATE_DTYPE), updated; seg: seg_cap x 48 B; desc: seg_cap
+        x 8 B; ares: n x 16 B (ACKGEN_RES_DTYPE); total: 2 x u64; work: at
+        least ackgen_work_bytes(n, max_id) bytes."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_ackgen_dev(self._h, _dptr(place), n, max_id, _dptr(idx), _dptr(seg_sid),
+                                            _dptr(seg_start), _dptr(nseg), _dptr(seg_stop),
+                                            None if ack_stop is None else _dptr(ack_stop), _dptr(state), _dptr(snd),
+                                            cur_ts & 0xFFFFFFFF, _dptr(tx), n_links, buf_off, buf_len, off_shift,
+                                            slot_bytes, _dptr(seg), _dptr(desc), seg_cap, _dptr(ares), _dptr(total),
+                                            _dptr(work), work.numel() * work.element_size(), st),
+                  "mtcp_gpu_ackgen_dev")
+
+    def ack_send_dev(self, place, n: int, max_id: int, idx, seg_sid, seg_start, nseg, seg_stop, ack_stop, state, snd,
+                     cur_ts: int, tx, links, buf, buf_off: int, off_shift: int, slot_bytes: int, seg, desc,
+                     seg_cap: int, ares, total, status, work, flags: int = 0, buf_len: int | None = None,
+                     stream=None) -> None:
+        """ackgen_dev, then tx_build_dev over all seg_cap records, on one stream.
+        buf_len: the bytes of buf the call may use (None: all of it)."""
+        room = buf.numel() * buf.element_size()
+        if buf_len is not None and not 0 <= buf_len <= room:
+            raise ValueError("buf_len: at most the bytes of buf")
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_ack_send_dev(self._h, _dptr(place), n, max_id, _dptr(idx), _dptr(seg_sid),
+                                              _dptr(seg_start), _dptr(nseg), _dptr(seg_stop),
+                                              None if ack_stop is None else _dptr(ack_stop), _dptr(state), _dptr(snd),
+                                              cur_ts & 0xFFFFFFFF, _dptr(tx), _dptr(links),
+                                              links.numel() * links.element_size() // 12, _dptr(buf), buf_off,
+                                              room if buf_len is None else buf_len, off_shift, slot_bytes, flags,
+                                              _dptr(seg), _dptr(desc), seg_cap, _dptr(ares), _dptr(total),
+                                              _dptr(status), _dptr(work), work.numel() * work.element_size(), st),
+                  "mtcp_gpu_ack_send_dev")
+
+    def ackgen(self, place: np.ndarray, max_id: int, idx: np.ndarray, seg_sid: np.ndarray, seg_start: np.ndarray,
+               seg_stop: np.ndarray, ack_stop, state: np.ndarray, snd: np.ndarray, cur_ts: int, tx: np.ndarray,
+               n_links: int, buf_len: int, seg_cap: int, buf_off: int = 0, off_shift: int = 0, slot_bytes: int = 0):
+        """mtcp_gpu_ackgen over the arrays group(), rcvwalk() and ackwalk()
+        returned: `tx` ((max_id + 1) x ACKGEN_STATE_DTYPE) is updated in place;
+        returns (seg, desc, ares, total), ares cut to the table's m entries."""
+        place = np.ascontiguousarray(place, dtype=RCV_PLACE_DTYPE)
+        n, m = len(place), len(seg_sid)
+        for a, dt, name in ((tx, ACKGEN_STATE_DTYPE, "tx"), (state, RCV_STATE_DTYPE, "state"), (snd, ACK_STATE_DTYPE, "snd")):
+            if a.dtype != dt or not a.flags.c_contiguous or len(a) != max_id + 1:
+                raise ValueError(f"{name}: (max_id + 1) contiguous records of its dtype")
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
+        idx, seg_sid, seg_start, seg_stop = u32(idx), u32(seg_sid), u32(seg_start), u32(seg_stop)
+        ack_stop = None if ack_stop is None else u32(ack_stop)
+        nseg = np.array([m], dtype=np.uint32)
+        seg, desc = np.zeros(seg_cap, dtype=TX_SEG_DTYPE), np.zeros(seg_cap, dtype=DESC_DTYPE)
+        ares, total = np.zeros(max(m, 1), dtype=ACKGEN_RES_DTYPE), np.zeros(2, dtype=np.uint64)
+        check(lib().mtcp_gpu_ackgen(self._h, place.ctypes.data, n, max_id, idx.ctypes.data, seg_sid.ctypes.data,
+                                    seg_start.ctypes.data, nseg.ctypes.data, seg_stop.ctypes.data,
+                                    None if ack_stop is None else ack_stop.ctypes.data, state.ctypes.data,
+                                    snd.ctypes.data, cur_ts & 0xFFFFFFFF, tx.ctypes.data, n_links, buf_off, buf_len,
+                                    off_shift, slot_bytes, seg.ctypes.data, desc.ctypes.data, seg_cap,
+                                    ares.ctypes.data, total.ctypes.data), "mtcp_gpu_ackgen")
+        return seg, desc, ares[:m], total
 
     # -- the payload copy behind the walk (tcp_ring_buffer.c:304-319; mtcp_gpu_rcvcopy.h) --
     @staticmethod
