@@ -39,6 +39,8 @@ EXPORTS = (
     "mtcp_gpu_ackwalk_work_bytes", "mtcp_gpu_ackwalk_short_len", "mtcp_gpu_ackwalk_dev", "mtcp_gpu_ackwalk",
     "mtcp_gpu_ackgen_work_bytes", "mtcp_gpu_ackgen_lane_len", "mtcp_gpu_ackgen_dev", "mtcp_gpu_ack_send_dev",
     "mtcp_gpu_ackgen",
+    "mtcp_gpu_datagen_work_bytes", "mtcp_gpu_datagen_lane_len", "mtcp_gpu_datagen_dev", "mtcp_gpu_data_send_dev",
+    "mtcp_gpu_datagen",
     "mtcp_gpu_rxq_pending", "mtcp_gpu_rxq_flush", "mtcp_gpu_rxq_flush_async", "mtcp_gpu_rxq_wait", "mtcp_gpu_rxq_wait_for", "mtcp_gpu_rxq_get", "mtcp_gpu_rxq_get16", "mtcp_gpu_rxq_frame", "mtcp_gpu_rxq_reset",
 )
 
@@ -148,6 +150,14 @@ def lib() -> ctypes.CDLL:
                                    u32, u32, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp], i32),
         "mtcp_gpu_ackgen": ([vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, u64, u64, u32, u32,
                              vp, vp, u32, vp, vp], i32),
+        "mtcp_gpu_datagen_work_bytes": ([u32, u32], u64),
+        "mtcp_gpu_datagen_lane_len": ([], u32),
+        "mtcp_gpu_datagen_dev": ([vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, u32, u64, u64, u32,
+                                  u32, ctypes.c_uint16, vp, vp, u32, vp, vp, vp, u64, vp], i32),
+        "mtcp_gpu_data_send_dev": ([vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp, u32, vp,
+                                    u64, u64, u32, u32, ctypes.c_uint16, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp], i32),
+        "mtcp_gpu_datagen": ([vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, u32, u64, u64, u32,
+                              u32, ctypes.c_uint16, vp, vp, u32, vp, vp], i32),
         "mtcp_gpu_rcvcopy_work_bytes": ([u32, u32], u64),
         "mtcp_gpu_rcvcopy_dev": ([vp, vp, u64, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64,
                                   vp], i32),

@@ -167,6 +167,21 @@ assert [ACKGEN_STATE_DTYPE.fields[f][1] for f in ACKGEN_STATE_DTYPE.names] == \
 ACKGEN_STATUS = ("NONE", "BAD", "DEFERRED", "IDLE", "NOT_TO_ACK", "SENT", "NO_ROOM")
 ACKGEN_ON_LIST, ACKGEN_NEED_WND_ADV, ACKGEN_FRAME_LEN = 0x1, 0x2, 66
 
+# include/mtcp_gpu_datagen.h: struct mtcp_gpu_datagen_state (where one stream's
+# send buffer lies in the payload arena and its list membership, 16 B:
+# d_dtx[max_id + 1] indexed by stream id) and struct mtcp_gpu_datagen_res (one
+# segment's result)
+DATAGEN_STATE_DTYPE = np.dtype([("sb_off", "<u8"), ("sb_base_seq", "<u4"), ("on_send_list", "u1"),
+                                ("on_control_list", "u1"), ("rsvd", "u1", (2,))])
+DATAGEN_RES_DTYPE = np.dtype([("first_seg", "<u4"), ("n_seg", "<u4"), ("bytes", "<u4"), ("status", "u1"),
+                              ("stop", "u1"), ("flags", "u1"), ("rsvd", "u1")])
+assert DATAGEN_STATE_DTYPE.itemsize == 16 and DATAGEN_RES_DTYPE.itemsize == 16
+DATAGEN_STATUS = ("NONE", "BAD", "DEFERRED", "IDLE", "CONTROL_WAIT", "NO_SNDBUF", "EMPTY", "BEHIND_HEAD", "BAD_BURST",
+                  "SENT", "WINDOW", "NO_ROOM")
+(DATAGEN_ON_LIST_BEFORE, DATAGEN_ON_LIST_AFTER, DATAGEN_RTO_ADD, DATAGEN_WACK_ENQUEUED,
+ DATAGEN_NEED_WND_ADV) = (1 << k for k in range(5))
+DATAGEN_MAX_DIST = 1 << 30
+
 # include/mtcp_gpu_rcvcopy.h: struct mtcp_gpu_rcv_buf (one stream's receive
 # buffer in the arena: what RBPut's byte work reads and writes of it,
 # tcp_ring_buffer.c:304-319) and the status bytes of d_cstat

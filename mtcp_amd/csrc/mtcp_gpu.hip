@@ -21,6 +21,7 @@
 #include "../../include/mtcp_gpu_rcvwalk.h"
 #include "../../include/mtcp_gpu_ackwalk.h"
 #include "../../include/mtcp_gpu_ackgen.h"
+#include "../../include/mtcp_gpu_datagen.h"
 #include "../../include/mtcp_gpu_rcvcopy.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
@@ -37,6 +38,7 @@
 #include "rcvwalk_kernels.hpp"
 #include "ackwalk_kernels.hpp"
 #include "ackgen_kernels.hpp"
+#include "datagen_kernels.hpp"
 #include "rcvcopy_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
@@ -2474,6 +2476,215 @@ int mtcp_gpu_ackgen(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcv_place *place, uint32_t
     memcpy(desc, h + (desc_off - tx_off), dbytes);
     if (m) memcpy(ares, h + (ares_off - tx_off), (uint64_t)m * sizeof(mtcp_gpu_ackgen_res));
     memcpy(total, h + (tot_off - tx_off), 16);
+    return MTCP_GPU_OK;
+}
+
+// ---- data tx segments from a walked rx batch ---------------------
+static_assert(sizeof(mtcp_gpu_datagen_state) == 16 && offsetof(mtcp_gpu_datagen_state, sb_base_seq) == 8 &&
+              offsetof(mtcp_gpu_datagen_state, on_send_list) == 12 && offsetof(mtcp_gpu_datagen_state, rsvd) == 14 &&
+              sizeof(mtcp_gpu_datagen_res) == 16 && offsetof(mtcp_gpu_datagen_res, status) == 12 &&
+              offsetof(mtcp_gpu_datagen_res, flags) == 14,
+              "datagen_step.hpp reads and writes the records as dwords");
+static_assert(offsetof(mtcp_gpu_ack_rec, flags) == 12 && offsetof(mtcp_gpu_ack_state, peer_wnd) == 12 &&
+              offsetof(mtcp_gpu_ack_state, cwnd) == 28 && offsetof(mtcp_gpu_ack_state, rto) == 36 &&
+              offsetof(mtcp_gpu_ack_state, ts_rto) == 40 && offsetof(mtcp_gpu_ack_state, sb_head_seq) == 64 &&
+              offsetof(mtcp_gpu_ack_state, mss) == 76 && offsetof(mtcp_gpu_ack_state, tcp_state) == 80 &&
+              offsetof(mtcp_gpu_ack_state, on_rto) == 85 && offsetof(mtcp_gpu_ack_state, user) == 88 &&
+              offsetof(mtcp_gpu_tx_burst, len) == 36 && offsetof(mtcp_gpu_tx_burst, tcp_window) == 52 &&
+              offsetof(mtcp_gpu_tx_burst, mss) == 56,
+              "datagen_burst_kernel's loads, datagen_burst's dwords, datagen_commit_kernel's stores");
+
+namespace {
+
+bool datagen_geom_ok(uint32_t n, uint32_t max_id, uint32_t n_links, uint64_t buf_off, uint32_t off_shift,
+                     uint32_t slot_bytes, uint32_t seg_cap) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || n > MTCP_GPU_TXSEG_MAX_BURSTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return false;
+    if (slot_bytes && slot_bytes < 67) return false;
+    return txseg_geom_ok(n, n_links, buf_off, off_shift, slot_bytes, seg_cap);
+}
+
+uint64_t datagen_work_total(uint32_t n) { return mg::datagen_work(n).f8_off + txseg_work(n).bytes; }
+
+bool datagen_dev_args_ok(const mtcp_gpu_ctx *ctx, const void *d_ack, const void *d_ack_stop, uint32_t n,
+                         uint32_t max_id, const void *d_idx, const void *d_seg_sid, const void *d_seg_start,
+                         const void *d_nseg, const void *d_seg_stop, const void *d_state, const void *d_snd,
+                         const void *d_tx, const void *d_dtx, uint32_t n_links, uint64_t buf_off, uint32_t off_shift,
+                         uint32_t slot_bytes, const void *d_seg, const void *d_desc, uint32_t seg_cap,
+                         const void *d_dres, const void *d_total, const void *d_work, uint64_t work_bytes) {
+    if (!ctx || (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        !datagen_geom_ok(n, max_id, n_links, buf_off, off_shift, slot_bytes, seg_cap))
+        return false;
+    if (!d_seg || !d_desc || !d_total || !d_work || (!d_ack != !d_ack_stop) ||
+        (n && (!d_idx || !d_seg_sid || !d_seg_start || !d_nseg || !d_seg_stop || !d_state || !d_snd || !d_tx ||
+               !d_dtx || !d_dres)))
+        return false;
+    if (((uintptr_t)d_ack & 15) || ((uintptr_t)d_ack_stop & 3) || ((uintptr_t)d_idx & 3) ||
+        ((uintptr_t)d_seg_sid & 3) || ((uintptr_t)d_seg_start & 3) || ((uintptr_t)d_nseg & 3) ||
+        ((uintptr_t)d_seg_stop & 3) || ((uintptr_t)d_state & 63) || ((uintptr_t)d_snd & 127) ||
+        ((uintptr_t)d_tx & 31) || ((uintptr_t)d_dtx & 15) || ((uintptr_t)d_seg & 7) || ((uintptr_t)d_desc & 7) ||
+        ((uintptr_t)d_dres & 15) || ((uintptr_t)d_total & 7) || ((uintptr_t)d_work & 15))
+        return false;
+    return work_bytes >= datagen_work_total(n);
+}
+
+}  // namespace
+
+uint32_t mtcp_gpu_datagen_lane_len(void) { return mg::kDatagenLaneMax; }
+
+uint64_t mtcp_gpu_datagen_work_bytes(uint32_t n, uint32_t max_id) {
+    if (n > MTCP_GPU_GROUP_MAX_PKTS || n > MTCP_GPU_TXSEG_MAX_BURSTS || max_id > MTCP_GPU_FLOWTAB_MAX_ID) return 0;
+    return datagen_work_total(n);
+}
+
+int mtcp_gpu_datagen_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_ack_rec *d_ack, const uint32_t *d_ack_stop, uint32_t n,
+                         uint32_t max_id, const uint32_t *d_idx, const uint32_t *d_seg_sid,
+                         const uint32_t *d_seg_start, const uint32_t *d_nseg, const uint32_t *d_seg_stop,
+                         const mtcp_gpu_rcv_state *d_state, mtcp_gpu_ack_state *d_snd, mtcp_gpu_ackgen_state *d_tx,
+                         mtcp_gpu_datagen_state *d_dtx, uint32_t cur_ts, uint64_t payload_bytes, uint32_t n_links,
+                         uint64_t buf_off, uint64_t buf_len, uint32_t off_shift, uint32_t slot_bytes,
+                         uint16_t max_mss, mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc, uint32_t seg_cap,
+                         mtcp_gpu_datagen_res *d_dres, uint64_t *d_total, void *d_work, uint64_t work_bytes,
+                         void *stream) {
+    if (!datagen_dev_args_ok(ctx, d_ack, d_ack_stop, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop,
+                             d_state, d_snd, d_tx, d_dtx, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc,
+                             seg_cap, d_dres, d_total, d_work, work_bytes))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const mg::DataGenWork w = mg::datagen_work(n);
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    mtcp_gpu_tx_burst *burst = reinterpret_cast<mtcp_gpu_tx_burst *>(work + w.burst_off);
+    mtcp_gpu_tx_burst_result *f8res = reinterpret_cast<mtcp_gpu_tx_burst_result *>(work + w.res_off);
+    uint32_t *park = reinterpret_cast<uint32_t *>(work + w.park_off);
+    const mg::DataGenParams P{n, max_id, n_links, cur_ts};
+    const dim3 block(mg::kBlock), grid((n + mg::kBlock - 1) / mg::kBlock);
+    if (n) {
+        hipLaunchKernelGGL(mg::datagen_burst_kernel<mg::kDatagenLaneMax>, grid, block, 0, st,
+                           reinterpret_cast<const uint8_t *>(d_ack), d_idx, P, d_seg_sid, d_seg_start, d_nseg,
+                           d_seg_stop, d_ack_stop, reinterpret_cast<const uint8_t *>(d_state),
+                           reinterpret_cast<const uint8_t *>(d_snd), reinterpret_cast<const uint8_t *>(d_tx),
+                           reinterpret_cast<const uint8_t *>(d_dtx), reinterpret_cast<uint8_t *>(burst), park);
+        if (!HIP_OK(hipGetLastError())) return MTCP_GPU_EIO;
+    }
+    const int rc = mtcp_gpu_tx_segment_dev(ctx, burst, n, payload_bytes, n_links, buf_off, buf_len, off_shift,
+                                           slot_bytes, max_mss, d_seg, d_desc, seg_cap, f8res, d_total,
+                                           work + w.f8_off, work_bytes - w.f8_off, st);
+    if (rc != MTCP_GPU_OK || !n) return rc;
+    hipLaunchKernelGGL(mg::datagen_commit_kernel, grid, block, 0, st, park, reinterpret_cast<const uint8_t *>(f8res), P,
+                       d_seg_sid, d_nseg, reinterpret_cast<uint8_t *>(d_snd), reinterpret_cast<uint8_t *>(d_tx),
+                       reinterpret_cast<uint8_t *>(d_dtx), d_dres);
+    ctx->last_kernel = "datagen_commit_kernel";
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+int mtcp_gpu_data_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_ack_rec *d_ack, const uint32_t *d_ack_stop, uint32_t n,
+                           uint32_t max_id, const uint32_t *d_idx, const uint32_t *d_seg_sid,
+                           const uint32_t *d_seg_start, const uint32_t *d_nseg, const uint32_t *d_seg_stop,
+                           const mtcp_gpu_rcv_state *d_state, mtcp_gpu_ack_state *d_snd, mtcp_gpu_ackgen_state *d_tx,
+                           mtcp_gpu_datagen_state *d_dtx, uint32_t cur_ts, const void *d_payload,
+                           uint64_t payload_bytes, const mtcp_gpu_tx_link *d_links, uint32_t n_links, void *d_buf,
+                           uint64_t buf_off, uint64_t buf_len, uint32_t off_shift, uint32_t slot_bytes,
+                           uint16_t max_mss, uint32_t flags, mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc,
+                           uint32_t seg_cap, mtcp_gpu_datagen_res *d_dres, uint64_t *d_total, uint8_t *d_status,
+                           void *d_work, uint64_t work_bytes, void *stream) {
+    // both calls' checks before either launches
+    if (!datagen_dev_args_ok(ctx, d_ack, d_ack_stop, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop,
+                             d_state, d_snd, d_tx, d_dtx, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc,
+                             seg_cap, d_dres, d_total, d_work, work_bytes) ||
+        !txbuild_args_ok(ctx, seg_cap, d_seg, d_payload, payload_bytes, d_links, n_links, d_buf, buf_len, d_desc,
+                         off_shift, flags, d_status) ||
+        ((uintptr_t)d_links & 3))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    const int rc = mtcp_gpu_datagen_dev(ctx, d_ack, d_ack_stop, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg,
+                                        d_seg_stop, d_state, d_snd, d_tx, d_dtx, cur_ts, payload_bytes, n_links,
+                                        buf_off, buf_len, off_shift, slot_bytes, max_mss, d_seg, d_desc, seg_cap,
+                                        d_dres, d_total, d_work, work_bytes, stream);
+    if (rc != MTCP_GPU_OK) return rc;
+    return mtcp_gpu_tx_build_dev(ctx, d_seg, seg_cap, d_payload, payload_bytes, d_links, n_links, d_buf, buf_len,
+                                 d_desc, off_shift, max_mss, flags, d_status, stream);
+}
+
+// Stage 0's chunk buffer: the inputs (ack, idx, seg_sid[m], seg_start[m + 1],
+// nseg, seg_stop[m], ack_stop[m] and state at their alignments), then in one
+// piece what comes back (snd, tx and dtx[max_id + 1], seg[seg_cap],
+// desc[seg_cap], dres[n], total[2]), then the workspace.
+int mtcp_gpu_datagen(mtcp_gpu_ctx *ctx, const mtcp_gpu_ack_rec *ack, const uint32_t *ack_stop, uint32_t n,
+                     uint32_t max_id, const uint32_t *idx, const uint32_t *seg_sid, const uint32_t *seg_start,
+                     const uint32_t *nseg, const uint32_t *seg_stop, const mtcp_gpu_rcv_state *state,
+                     mtcp_gpu_ack_state *snd, mtcp_gpu_ackgen_state *tx, mtcp_gpu_datagen_state *dtx, uint32_t cur_ts,
+                     uint64_t payload_bytes, uint32_t n_links, uint64_t buf_off, uint64_t buf_len,
+                     uint32_t off_shift, uint32_t slot_bytes, uint16_t max_mss, mtcp_gpu_tx_seg *seg,
+                     mtcp_gpu_desc *desc, uint32_t seg_cap, mtcp_gpu_datagen_res *dres, uint64_t total[2]) {
+    if (!ctx || (ctx->flags & MTCP_GPU_F_COMPACT) ||
+        !datagen_geom_ok(n, max_id, n_links, buf_off, off_shift, slot_bytes, seg_cap) || !seg || !desc || !total ||
+        (!ack != !ack_stop) ||
+        (n && (!idx || !seg_sid || !seg_start || !nseg || !seg_stop || !state || !snd || !tx || !dtx || !dres)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const uint32_t m = n ? std::min(nseg[0], n) : 0u;
+    const uint64_t ids = n ? (uint64_t)max_id + 1 : 0;
+    const uint64_t abytes = (uint64_t)n * sizeof(mtcp_gpu_ack_rec), ibytes = (uint64_t)n * sizeof(uint32_t);
+    const uint64_t mbytes = (uint64_t)m * sizeof(uint32_t);
+    const uint64_t stbytes = ids * sizeof(mtcp_gpu_rcv_state), snbytes = ids * sizeof(mtcp_gpu_ack_state);
+    const uint64_t txbytes = ids * sizeof(mtcp_gpu_ackgen_state), dtbytes = ids * sizeof(mtcp_gpu_datagen_state);
+    const uint64_t sgbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_tx_seg), dbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_desc);
+    const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_datagen_res);
+    const uint64_t ack_off = 0, idx_off = ack_off + abytes, sid_off = idx_off + pad16(ibytes);
+    const uint64_t start_off = sid_off + pad16(mbytes), nseg_off = start_off + pad16(mbytes + 4);
+    const uint64_t stop_off = nseg_off + 16, astop_off = stop_off + pad16(mbytes);
+    const uint64_t state_off = (astop_off + pad16(mbytes) + 127) & ~127ull;
+    const uint64_t snd_off = (state_off + stbytes + 127) & ~127ull;          // what comes back begins here
+    const uint64_t tx_off = snd_off + snbytes, dtx_off = tx_off + txbytes;    // multiples of 128 and of 32
+    const uint64_t seg_off = dtx_off + dtbytes, desc_off = seg_off + sgbytes, res_off = desc_off + pad16(dbytes);
+    const uint64_t tot_off = res_off + rbytes, back_bytes = tot_off + 16 - snd_off;
+    const uint64_t work_off = tot_off + 16, wbytes = datagen_work_total(n);
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, grown(work_off + wbytes, s.buf_cap), 0, dl);
+    if (rc == MTCP_GPU_OK)
+        rc = stage_host(ctx, s, dl.bounded ? grown(seg_off, s.h_in_cap) : 0, grown(back_bytes, s.h_out_cap), dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    auto at = [&](uint64_t off) { return s.d_buf + off; };
+    auto u32p = [&](uint64_t off) { return reinterpret_cast<const uint32_t *>(at(off)); };
+    Call hc(s, dl, {ctx, dl});
+    if (n) {
+        if (ack) hc.up(at(ack_off), ack, abytes);
+        hc.up(at(idx_off), idx, ibytes);
+        hc.up(at(sid_off), seg_sid, mbytes);
+        hc.up(at(start_off), seg_start, mbytes + 4);
+        hc.up(at(nseg_off), &m, sizeof(uint32_t));
+        hc.up(at(stop_off), seg_stop, mbytes);
+        if (ack_stop) hc.up(at(astop_off), ack_stop, mbytes);
+        hc.up(at(state_off), state, stbytes);
+        hc.up(at(snd_off), snd, snbytes);
+        hc.up(at(tx_off), tx, txbytes);
+        hc.up(at(dtx_off), dtx, dtbytes);
+    }
+    if (hc.ok())
+        hc.note(mtcp_gpu_datagen_dev(ctx, ack ? reinterpret_cast<const mtcp_gpu_ack_rec *>(at(ack_off)) : nullptr,
+                                     ack_stop ? u32p(astop_off) : nullptr, n, max_id, u32p(idx_off), u32p(sid_off),
+                                     u32p(start_off), u32p(nseg_off), u32p(stop_off),
+                                     reinterpret_cast<const mtcp_gpu_rcv_state *>(at(state_off)),
+                                     reinterpret_cast<mtcp_gpu_ack_state *>(at(snd_off)),
+                                     reinterpret_cast<mtcp_gpu_ackgen_state *>(at(tx_off)),
+                                     reinterpret_cast<mtcp_gpu_datagen_state *>(at(dtx_off)), cur_ts, payload_bytes,
+                                     n_links, buf_off, buf_len, off_shift, slot_bytes, max_mss,
+                                     reinterpret_cast<mtcp_gpu_tx_seg *>(at(seg_off)),
+                                     reinterpret_cast<mtcp_gpu_desc *>(at(desc_off)), seg_cap,
+                                     reinterpret_cast<mtcp_gpu_datagen_res *>(at(res_off)),
+                                     reinterpret_cast<uint64_t *>(at(tot_off)), at(work_off), wbytes, s.stream));
+    const uint8_t *h = hc.down_pinned(at(snd_off), back_bytes);
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+    if (snbytes) memcpy(snd, h, snbytes);
+    if (txbytes) memcpy(tx, h + (tx_off - snd_off), txbytes);
+    if (dtbytes) memcpy(dtx, h + (dtx_off - snd_off), dtbytes);
+    memcpy(seg, h + (seg_off - snd_off), sgbytes);
+    memcpy(desc, h + (desc_off - snd_off), dbytes);
+    if (m) memcpy(dres, h + (res_off - snd_off), (uint64_t)m * sizeof(mtcp_gpu_datagen_res));
+    memcpy(total, h + (tot_off - snd_off), 16);
     return MTCP_GPU_OK;
 }
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, DATAGEN_RES_DTYPE, DATAGEN_STATE_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -494,6 +494,93 @@ class Context:
                                     off_shift, slot_bytes, seg.ctypes.data, desc.ctypes.data, seg_cap,
                                     ares.ctypes.data, total.ctypes.data), "mtcp_gpu_ackgen")
         return seg, desc, ares[:m], total
+
+    # -- data tx segments from a walked batch (tcp_out.c:607-660, :357-449; mtcp_gpu_datagen.h) --
+    @staticmethod
+    def datagen_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_datagen_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_datagen_work_bytes(n, max_id)
+
+    @staticmethod
+    def datagen_lane_len() -> int:
+        return lib().mtcp_gpu_datagen_lane_len()
+
+    def datagen_dev(self, ack, ack_stop, n: int, max_id: int, idx, seg_sid, seg_start, nseg, seg_stop, state, snd, tx,
+                    dtx, cur_ts: int, payload_bytes: int, n_links: int, buf_off: int, buf_len: int, off_shift: int,
+                    slot_bytes: int, seg, desc, seg_cap: int, dres, total, work, max_mss: int = 0, stream=None) -> None:
+        """ack, ack_stop: as ackwalk_dev wrote them, or None for both; idx,
+        seg_sid, seg_start, nseg: as group_dev wrote them; seg_stop: as
+        rcvwalk_dev wrote it; state: the receive walk's (max_id + 1) records;
+        snd ((max_id + 1) x 128 B), tx (x 32 B) and dtx (x 16 B,
+        DATAGEN_STATE_DTYPE): updated; seg: seg_cap x 48 B; desc: seg_cap x 8 B;
+        dres: n x 16 B (DATAGEN_RES_DTYPE); total: 2 x u64; work: at least
+        datagen_work_bytes(n, max_id) bytes."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_datagen_dev(self._h, None if ack is None else _dptr(ack),
+                                             None if ack_stop is None else _dptr(ack_stop), n, max_id, _dptr(idx),
+                                             _dptr(seg_sid), _dptr(seg_start), _dptr(nseg), _dptr(seg_stop),
+                                             _dptr(state), _dptr(snd), _dptr(tx), _dptr(dtx), cur_ts & 0xFFFFFFFF,
+                                             payload_bytes, n_links, buf_off, buf_len, off_shift, slot_bytes, max_mss,
+                                             _dptr(seg), _dptr(desc), seg_cap, _dptr(dres), _dptr(total), _dptr(work),
+                                             work.numel() * work.element_size(), st), "mtcp_gpu_datagen_dev")
+
+    def data_send_dev(self, ack, ack_stop, n: int, max_id: int, idx, seg_sid, seg_start, nseg, seg_stop, state, snd,
+                      tx, dtx, cur_ts: int, payload, links, buf, buf_off: int, off_shift: int, slot_bytes: int, seg,
+                      desc, seg_cap: int, dres, total, status, work, max_mss: int = 0, flags: int = 0,
+                      buf_len: int | None = None, payload_bytes: int | None = None, stream=None) -> None:
+        """datagen_dev, then tx_build_dev over all seg_cap records, on one
+        stream.  payload: the arena the send buffers live in; buf_len: the
+        bytes of buf the call may use (None: all of it)."""
+        room = buf.numel() * buf.element_size()
+        if buf_len is not None and not 0 <= buf_len <= room:
+            raise ValueError("buf_len: at most the bytes of buf")
+        pbytes = payload.numel() * payload.element_size()
+        if payload_bytes is not None and not 0 <= payload_bytes <= pbytes:
+            raise ValueError("payload_bytes: at most the bytes of payload")
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_data_send_dev(self._h, None if ack is None else _dptr(ack),
+                                               None if ack_stop is None else _dptr(ack_stop), n, max_id, _dptr(idx),
+                                               _dptr(seg_sid), _dptr(seg_start), _dptr(nseg), _dptr(seg_stop),
+                                               _dptr(state), _dptr(snd), _dptr(tx), _dptr(dtx), cur_ts & 0xFFFFFFFF,
+                                               _dptr(payload), pbytes if payload_bytes is None else payload_bytes,
+                                               _dptr(links), links.numel() * links.element_size() // 12, _dptr(buf),
+                                               buf_off, room if buf_len is None else buf_len, off_shift, slot_bytes,
+                                               max_mss, flags, _dptr(seg), _dptr(desc), seg_cap, _dptr(dres),
+                                               _dptr(total), _dptr(status), _dptr(work),
+                                               work.numel() * work.element_size(), st), "mtcp_gpu_data_send_dev")
+
+    def datagen(self, ack, ack_stop, max_id: int, idx: np.ndarray, seg_sid: np.ndarray, seg_start: np.ndarray,
+                seg_stop: np.ndarray, state: np.ndarray, snd: np.ndarray, tx: np.ndarray, dtx: np.ndarray, cur_ts: int,
+                payload_bytes: int, n_links: int, buf_len: int, seg_cap: int, buf_off: int = 0, off_shift: int = 0,
+                slot_bytes: int = 0, max_mss: int = 0):
+        """mtcp_gpu_datagen over the arrays group(), rcvwalk() and ackwalk()
+        returned (ack and ack_stop may both be None): `snd`, `tx` and `dtx`
+        ((max_id + 1) records each) are updated in place; returns (seg, desc,
+        dres, total), dres cut to the table's m entries."""
+        n, m = len(idx), len(seg_sid)
+        for a, dt, name in ((tx, ACKGEN_STATE_DTYPE, "tx"), (state, RCV_STATE_DTYPE, "state"),
+                            (snd, ACK_STATE_DTYPE, "snd"), (dtx, DATAGEN_STATE_DTYPE, "dtx")):
+            if a.dtype != dt or not a.flags.c_contiguous or len(a) != max_id + 1:
+                raise ValueError(f"{name}: (max_id + 1) contiguous records of its dtype")
+        if (ack is None) != (ack_stop is None):
+            raise ValueError("ack and ack_stop: both or neither")
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
+        idx, seg_sid, seg_start, seg_stop = u32(idx), u32(seg_sid), u32(seg_start), u32(seg_stop)
+        if ack is not None:
+            ack, ack_stop = np.ascontiguousarray(ack, dtype=ACK_REC_DTYPE), u32(ack_stop)
+            if len(ack) != n:
+                raise ValueError("ack: one record per packet")
+        nseg = np.array([m], dtype=np.uint32)
+        seg, desc = np.zeros(seg_cap, dtype=TX_SEG_DTYPE), np.zeros(seg_cap, dtype=DESC_DTYPE)
+        dres, total = np.zeros(max(m, 1), dtype=DATAGEN_RES_DTYPE), np.zeros(2, dtype=np.uint64)
+        check(lib().mtcp_gpu_datagen(self._h, None if ack is None else ack.ctypes.data,
+                                     None if ack_stop is None else ack_stop.ctypes.data, n, max_id, idx.ctypes.data,
+                                     seg_sid.ctypes.data, seg_start.ctypes.data, nseg.ctypes.data,
+                                     seg_stop.ctypes.data, state.ctypes.data, snd.ctypes.data, tx.ctypes.data,
+                                     dtx.ctypes.data, cur_ts & 0xFFFFFFFF, payload_bytes, n_links, buf_off, buf_len,
+                                     off_shift, slot_bytes, max_mss, seg.ctypes.data, desc.ctypes.data, seg_cap,
+                                     dres.ctypes.data, total.ctypes.data), "mtcp_gpu_datagen")
+        return seg, desc, dres[:m], total
 
     # -- the payload copy behind the walk (tcp_ring_buffer.c:304-319; mtcp_gpu_rcvcopy.h) --
     @staticmethod
