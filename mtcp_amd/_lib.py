@@ -41,6 +41,8 @@ EXPORTS = (
     "mtcp_gpu_ackgen",
     "mtcp_gpu_datagen_work_bytes", "mtcp_gpu_datagen_lane_len", "mtcp_gpu_datagen_dev", "mtcp_gpu_data_send_dev",
     "mtcp_gpu_datagen",
+    "mtcp_gpu_rto_sweep_work_bytes", "mtcp_gpu_rto_sweep_tile", "mtcp_gpu_rto_sweep_dev", "mtcp_gpu_rto_sweep",
+    "mtcp_gpu_rto_send_dev",
     "mtcp_gpu_rxq_pending", "mtcp_gpu_rxq_flush", "mtcp_gpu_rxq_flush_async", "mtcp_gpu_rxq_wait", "mtcp_gpu_rxq_wait_for", "mtcp_gpu_rxq_get", "mtcp_gpu_rxq_get16", "mtcp_gpu_rxq_frame", "mtcp_gpu_rxq_reset",
 )
 
@@ -158,6 +160,13 @@ def lib() -> ctypes.CDLL:
                                     u64, u64, u32, u32, ctypes.c_uint16, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp], i32),
         "mtcp_gpu_datagen": ([vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, u32, u64, u64, u32,
                               u32, ctypes.c_uint16, vp, vp, u32, vp, vp], i32),
+        "mtcp_gpu_rto_sweep_work_bytes": ([u32, u32], u64),
+        "mtcp_gpu_rto_sweep_tile": ([], u32),
+        "mtcp_gpu_rto_sweep_dev": ([vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp], i32),
+        "mtcp_gpu_rto_sweep": ([vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp], i32),
+        "mtcp_gpu_rto_send_dev": ([vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp,
+                                   u32, vp, u64, u64, u32, u32, ctypes.c_uint16, u32, vp, vp, u32, vp, vp, vp, vp, u64,
+                                   vp], i32),
         "mtcp_gpu_rcvcopy_work_bytes": ([u32, u32], u64),
         "mtcp_gpu_rcvcopy_dev": ([vp, vp, u64, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64,
                                   vp], i32),

@@ -182,6 +182,14 @@ DATAGEN_STATUS = ("NONE", "BAD", "DEFERRED", "IDLE", "CONTROL_WAIT", "NO_SNDBUF"
  DATAGEN_NEED_WND_ADV) = (1 << k for k in range(5))
 DATAGEN_MAX_DIST = 1 << 30
 
+# include/mtcp_gpu_rtosweep.h: struct mtcp_gpu_rto_rec (one handled stream of a
+# retransmission-timeout sweep, 16 B: d_rto[j] for j < handled, in ascending id)
+RTO_REC_DTYPE = np.dtype([("sid", "<u4"), ("rto", "<u4"), ("nrtx", "u1"), ("verdict", "u1"), ("flags", "u1"),
+                          ("rsvd0", "u1"), ("rsvd1", "<u4")])
+assert RTO_REC_DTYPE.itemsize == 16
+RTO_VERDICTS = ("NONE", "BAD", "DEFER_STATE", "LOST", "RETRANSMIT")
+RTO_SEND_LIST_ADD, RTO_MAX_BACKOFF, RTO_ST_CLOSED = 0x01, 7, 0
+
 # include/mtcp_gpu_rcvcopy.h: struct mtcp_gpu_rcv_buf (one stream's receive
 # buffer in the arena: what RBPut's byte work reads and writes of it,
 # tcp_ring_buffer.c:304-319) and the status bytes of d_cstat

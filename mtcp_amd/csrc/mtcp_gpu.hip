@@ -22,6 +22,7 @@
 #include "../../include/mtcp_gpu_ackwalk.h"
 #include "../../include/mtcp_gpu_ackgen.h"
 #include "../../include/mtcp_gpu_datagen.h"
+#include "../../include/mtcp_gpu_rtosweep.h"
 #include "../../include/mtcp_gpu_rcvcopy.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
@@ -39,6 +40,7 @@
 #include "ackwalk_kernels.hpp"
 #include "ackgen_kernels.hpp"
 #include "datagen_kernels.hpp"
+#include "rtosweep_kernels.hpp"
 #include "rcvcopy_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
@@ -2685,6 +2687,161 @@ int mtcp_gpu_datagen(mtcp_gpu_ctx *ctx, const mtcp_gpu_ack_rec *ack, const uint3
     memcpy(desc, h + (desc_off - snd_off), dbytes);
     if (m) memcpy(dres, h + (res_off - snd_off), (uint64_t)m * sizeof(mtcp_gpu_datagen_res));
     memcpy(total, h + (tot_off - snd_off), 16);
+    return MTCP_GPU_OK;
+}
+
+// ---- the retransmission-timeout sweep over device send states ----
+static_assert(sizeof(mtcp_gpu_rto_rec) == 16 && offsetof(mtcp_gpu_rto_rec, rto) == 4 &&
+              offsetof(mtcp_gpu_rto_rec, nrtx) == 8 && offsetof(mtcp_gpu_rto_rec, verdict) == 9 &&
+              offsetof(mtcp_gpu_rto_rec, flags) == 10 && offsetof(mtcp_gpu_rto_rec, rsvd1) == 12,
+              "rto_step.hpp writes the record as dwords");
+static_assert(offsetof(mtcp_gpu_ack_state, snd_una) == 4 && offsetof(mtcp_gpu_ack_state, ssthresh) == 32 &&
+              offsetof(mtcp_gpu_ack_state, srtt) == 44 && offsetof(mtcp_gpu_ack_state, rttvar) == 56 &&
+              offsetof(mtcp_gpu_ack_state, sb_len) == 68 && offsetof(mtcp_gpu_ack_state, nrtx) == 84 &&
+              offsetof(mtcp_gpu_ack_state, has_sndbuf) == 86,
+              "rto_lane_due's and rto_handle's loads and stores");
+
+namespace {
+
+bool rto_geom_ok(uint32_t max_id, uint32_t cap) {
+    return cap != 0 && cap <= MTCP_GPU_TXSEG_MAX_BURSTS && max_id <= MTCP_GPU_FLOWTAB_MAX_ID;
+}
+
+bool rto_dev_args_ok(const mtcp_gpu_ctx *ctx, uint32_t max_id, const void *d_snd, const void *d_dtx, uint32_t cap,
+                     const void *d_rto, const void *d_seg_sid, const void *d_seg_start, const void *d_seg_stop,
+                     const void *d_nseg, const void *d_total, const void *d_work, uint64_t work_bytes) {
+    if (!ctx || !rto_geom_ok(max_id, cap)) return false;
+    if (!d_snd || !d_dtx || !d_rto || !d_seg_sid || !d_seg_start || !d_seg_stop || !d_nseg || !d_total || !d_work)
+        return false;
+    if (((uintptr_t)d_snd & 127) || ((uintptr_t)d_dtx & 15) || ((uintptr_t)d_rto & 15) ||
+        ((uintptr_t)d_seg_sid & 3) || ((uintptr_t)d_seg_start & 3) || ((uintptr_t)d_seg_stop & 3) ||
+        ((uintptr_t)d_nseg & 3) || ((uintptr_t)d_total & 7) || ((uintptr_t)d_work & 15))
+        return false;
+    return work_bytes >= mg::rto_sweep_work(max_id).bytes;
+}
+
+}  // namespace
+
+uint32_t mtcp_gpu_rto_sweep_tile(void) { return mg::kRtoTile; }
+
+uint64_t mtcp_gpu_rto_sweep_work_bytes(uint32_t max_id, uint32_t cap) {
+    if (!rto_geom_ok(max_id, cap)) return 0;
+    return mg::rto_sweep_work(max_id).bytes;
+}
+
+int mtcp_gpu_rto_sweep_dev(mtcp_gpu_ctx *ctx, uint32_t max_id, mtcp_gpu_ack_state *d_snd,
+                           mtcp_gpu_datagen_state *d_dtx, uint32_t cur_ts, uint32_t cap, mtcp_gpu_rto_rec *d_rto,
+                           uint32_t *d_seg_sid, uint32_t *d_seg_start, uint32_t *d_seg_stop, uint32_t *d_nseg,
+                           uint64_t *d_total, void *d_work, uint64_t work_bytes, void *stream) {
+    if (!rto_dev_args_ok(ctx, max_id, d_snd, d_dtx, cap, d_rto, d_seg_sid, d_seg_start, d_seg_stop, d_nseg, d_total,
+                         d_work, work_bytes))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = pick(ctx, stream);
+    const mg::RtoSweepWork w = mg::rto_sweep_work(max_id);
+    const mg::RtoSweepParams P{max_id, cap, cur_ts};
+    uint8_t *snd = reinterpret_cast<uint8_t *>(d_snd), *dtx = reinterpret_cast<uint8_t *>(d_dtx);
+    const dim3 block(mg::kBlock);
+    if (w.ntiles == 1 && cap <= mg::kRtoTile) {
+        hipLaunchKernelGGL(mg::rto_one_kernel, dim3(1), block, 0, st, P, snd, dtx, d_rto, d_seg_sid,
+                           d_seg_start, d_seg_stop, d_nseg, d_total);
+        ctx->last_kernel = "rto_one_kernel";
+        return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+    }
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint64_t *ballots = reinterpret_cast<uint64_t *>(work + w.ballot_off);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(work + w.cnt_off);
+    uint32_t *tot = reinterpret_cast<uint32_t *>(work + w.tot_off);
+    hipLaunchKernelGGL(mg::rto_count_kernel, dim3(w.ntiles), block, 0, st, snd, P, ballots, cnt);
+    hipLaunchKernelGGL(mg::steer_scan_kernel, dim3(1), block, 0, st, cnt, w.nwaves, tot);
+    hipLaunchKernelGGL(mg::rto_emit_kernel, dim3(w.ntiles), block, 0, st, ballots, cnt, tot, P, snd, dtx, d_rto,
+                       d_seg_sid, d_seg_start, d_seg_stop, d_nseg, d_total);
+    ctx->last_kernel = "rto_emit_kernel";
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+int mtcp_gpu_rto_send_dev(mtcp_gpu_ctx *ctx, uint32_t max_id, mtcp_gpu_ack_state *d_snd,
+                          mtcp_gpu_datagen_state *d_dtx, uint32_t cur_ts, uint32_t cap, mtcp_gpu_rto_rec *d_rto,
+                          uint32_t *d_seg_sid, uint32_t *d_seg_start, uint32_t *d_seg_stop, uint32_t *d_nseg,
+                          uint64_t *d_total, void *d_rwork, uint64_t rwork_bytes, const uint32_t *d_idx,
+                          const mtcp_gpu_rcv_state *d_state, mtcp_gpu_ackgen_state *d_tx, const void *d_payload,
+                          uint64_t payload_bytes, const mtcp_gpu_tx_link *d_links, uint32_t n_links, void *d_buf,
+                          uint64_t buf_off, uint64_t buf_len, uint32_t off_shift, uint32_t slot_bytes,
+                          uint16_t max_mss, uint32_t flags, mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc,
+                          uint32_t seg_cap, mtcp_gpu_datagen_res *d_dres, uint64_t *d_dtotal, uint8_t *d_status,
+                          void *d_work, uint64_t work_bytes, void *stream) {
+    // both calls' checks before either launches
+    if (!rto_dev_args_ok(ctx, max_id, d_snd, d_dtx, cap, d_rto, d_seg_sid, d_seg_start, d_seg_stop, d_nseg, d_total,
+                         d_rwork, rwork_bytes) ||
+        !datagen_dev_args_ok(ctx, nullptr, nullptr, cap, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop,
+                             d_state, d_snd, d_tx, d_dtx, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc,
+                             seg_cap, d_dres, d_dtotal, d_work, work_bytes) ||
+        !txbuild_args_ok(ctx, seg_cap, d_seg, d_payload, payload_bytes, d_links, n_links, d_buf, buf_len, d_desc,
+                         off_shift, flags, d_status) ||
+        ((uintptr_t)d_links & 3))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    const int rc = mtcp_gpu_rto_sweep_dev(ctx, max_id, d_snd, d_dtx, cur_ts, cap, d_rto, d_seg_sid, d_seg_start,
+                                          d_seg_stop, d_nseg, d_total, d_rwork, rwork_bytes, stream);
+    if (rc != MTCP_GPU_OK) return rc;
+    return mtcp_gpu_data_send_dev(ctx, nullptr, nullptr, cap, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg,
+                                  d_seg_stop, d_state, d_snd, d_tx, d_dtx, cur_ts, d_payload, payload_bytes, d_links,
+                                  n_links, d_buf, buf_off, buf_len, off_shift, slot_bytes, max_mss, flags, d_seg,
+                                  d_desc, seg_cap, d_dres, d_dtotal, d_status, d_work, work_bytes, stream);
+}
+
+// Stage 0's chunk buffer: in one piece what goes up and comes back (snd and
+// dtx[max_id + 1]) and what comes back only (rto[cap], seg_sid[cap],
+// seg_start[cap + 1], seg_stop[cap], nseg, total[2]), then the workspace.
+int mtcp_gpu_rto_sweep(mtcp_gpu_ctx *ctx, uint32_t max_id, mtcp_gpu_ack_state *snd, mtcp_gpu_datagen_state *dtx,
+                       uint32_t cur_ts, uint32_t cap, mtcp_gpu_rto_rec *rto, uint32_t *seg_sid, uint32_t *seg_start,
+                       uint32_t *seg_stop, uint32_t *nseg, uint64_t total[2]) {
+    if (!ctx || !rto_geom_ok(max_id, cap) || !snd || !dtx || !rto || !seg_sid || !seg_start || !seg_stop || !nseg ||
+        !total)
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const uint64_t ids = (uint64_t)max_id + 1;
+    const uint64_t snbytes = ids * sizeof(mtcp_gpu_ack_state), dtbytes = ids * sizeof(mtcp_gpu_datagen_state);
+    const uint64_t rbytes = (uint64_t)cap * sizeof(mtcp_gpu_rto_rec), cbytes = (uint64_t)cap * sizeof(uint32_t);
+    const uint64_t snd_off = 0, dtx_off = snd_off + snbytes, rto_off = dtx_off + dtbytes;   // multiples of 128 and of 16
+    const uint64_t sid_off = rto_off + rbytes, start_off = sid_off + pad16(cbytes);
+    const uint64_t stop_off = start_off + pad16(cbytes + 4), nseg_off = stop_off + pad16(cbytes);
+    const uint64_t tot_off = nseg_off + 16, back_bytes = tot_off + 16;
+    const uint64_t work_off = back_bytes, wbytes = mg::rto_sweep_work(max_id).bytes;
+    Stage &s = ctx->stage[0];
+    int rc = stage_reserve(ctx, s, grown(work_off + wbytes, s.buf_cap), 0, dl);
+    if (rc == MTCP_GPU_OK)
+        rc = stage_host(ctx, s, dl.bounded ? grown(rto_off, s.h_in_cap) : 0, grown(back_bytes, s.h_out_cap), dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    auto at = [&](uint64_t off) { return s.d_buf + off; };
+    auto u32p = [&](uint64_t off) { return reinterpret_cast<uint32_t *>(at(off)); };
+    Call hc(s, dl, {ctx, dl});
+    hc.up(at(snd_off), snd, snbytes);
+    hc.up(at(dtx_off), dtx, dtbytes);
+    if (hc.ok())
+        hc.note(mtcp_gpu_rto_sweep_dev(ctx, max_id, reinterpret_cast<mtcp_gpu_ack_state *>(at(snd_off)),
+                                       reinterpret_cast<mtcp_gpu_datagen_state *>(at(dtx_off)), cur_ts, cap,
+                                       reinterpret_cast<mtcp_gpu_rto_rec *>(at(rto_off)), u32p(sid_off),
+                                       u32p(start_off), u32p(stop_off), u32p(nseg_off),
+                                       reinterpret_cast<uint64_t *>(at(tot_off)), at(work_off), wbytes, s.stream));
+    const uint8_t *h = hc.down_pinned(at(snd_off), back_bytes);
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+    uint32_t handled;
+    memcpy(&handled, h + nseg_off, sizeof(handled));
+    handled = std::min(handled, cap);
+    memcpy(snd, h + snd_off, snbytes);
+    memcpy(dtx, h + dtx_off, dtbytes);
+    if (handled) {
+        memcpy(rto, h + rto_off, (uint64_t)handled * sizeof(mtcp_gpu_rto_rec));
+        memcpy(seg_sid, h + sid_off, (uint64_t)handled * sizeof(uint32_t));
+    }
+    memcpy(seg_start, h + start_off, cbytes + 4);
+    memcpy(seg_stop, h + stop_off, cbytes);
+    memcpy(nseg, h + nseg_off, sizeof(uint32_t));
+    memcpy(total, h + tot_off, 16);
     return MTCP_GPU_OK;
 }
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, DATAGEN_RES_DTYPE, DATAGEN_STATE_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, DATAGEN_RES_DTYPE, DATAGEN_STATE_DTYPE, RTO_REC_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -581,6 +581,76 @@ class Context:
                                      off_shift, slot_bytes, max_mss, seg.ctypes.data, desc.ctypes.data, seg_cap,
                                      dres.ctypes.data, total.ctypes.data), "mtcp_gpu_datagen")
         return seg, desc, dres[:m], total
+
+    # -- the retransmission-timeout sweep (timer.c:363-419, :176-337; mtcp_gpu_rtosweep.h) --
+    @staticmethod
+    def rto_sweep_work_bytes(max_id: int, cap: int) -> int:
+        """mtcp_gpu_rto_sweep_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_rto_sweep_work_bytes(max_id, cap)
+
+    @staticmethod
+    def rto_sweep_tile() -> int:
+        return lib().mtcp_gpu_rto_sweep_tile()
+
+    def rto_sweep_dev(self, max_id: int, snd, dtx, cur_ts: int, cap: int, rto, seg_sid, seg_start, seg_stop, nseg,
+                      total, work, stream=None) -> None:
+        """snd ((max_id + 1) x 128 B) and dtx (x 16 B): updated; rto: cap x 16 B
+        (RTO_REC_DTYPE); seg_sid: cap x u32; seg_start: (cap + 1) x u32;
+        seg_stop: cap x u32; nseg: 1 x u32; total: 2 x u64 (due, handled);
+        work: at least rto_sweep_work_bytes(max_id, cap) bytes."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_rto_sweep_dev(self._h, max_id, _dptr(snd), _dptr(dtx), cur_ts & 0xFFFFFFFF, cap,
+                                               _dptr(rto), _dptr(seg_sid), _dptr(seg_start), _dptr(seg_stop),
+                                               _dptr(nseg), _dptr(total), _dptr(work),
+                                               work.numel() * work.element_size(), st), "mtcp_gpu_rto_sweep_dev")
+
+    def rto_send_dev(self, max_id: int, snd, dtx, cur_ts: int, cap: int, rto, seg_sid, seg_start, seg_stop, nseg,
+                     total, rwork, idx, state, tx, payload, links, buf, buf_off: int, off_shift: int,
+                     slot_bytes: int, seg, desc, seg_cap: int, dres, dtotal, status, work, max_mss: int = 0,
+                     flags: int = 0, buf_len: int | None = None, payload_bytes: int | None = None,
+                     stream=None) -> None:
+        """rto_sweep_dev, then data_send_dev over the table the sweep wrote
+        (ack and ack_stop None, n = cap), on one stream.  idx: cap x u32, any
+        values; rwork: the sweep's workspace; work: the data send's, at least
+        datagen_work_bytes(cap, max_id) bytes; dtotal: the data send's totals."""
+        room = buf.numel() * buf.element_size()
+        if buf_len is not None and not 0 <= buf_len <= room:
+            raise ValueError("buf_len: at most the bytes of buf")
+        pbytes = payload.numel() * payload.element_size()
+        if payload_bytes is not None and not 0 <= payload_bytes <= pbytes:
+            raise ValueError("payload_bytes: at most the bytes of payload")
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_rto_send_dev(self._h, max_id, _dptr(snd), _dptr(dtx), cur_ts & 0xFFFFFFFF, cap,
+                                              _dptr(rto), _dptr(seg_sid), _dptr(seg_start), _dptr(seg_stop),
+                                              _dptr(nseg), _dptr(total), _dptr(rwork),
+                                              rwork.numel() * rwork.element_size(), _dptr(idx), _dptr(state),
+                                              _dptr(tx), _dptr(payload),
+                                              pbytes if payload_bytes is None else payload_bytes, _dptr(links),
+                                              links.numel() * links.element_size() // 12, _dptr(buf), buf_off,
+                                              room if buf_len is None else buf_len, off_shift, slot_bytes, max_mss,
+                                              flags, _dptr(seg), _dptr(desc), seg_cap, _dptr(dres), _dptr(dtotal),
+                                              _dptr(status), _dptr(work), work.numel() * work.element_size(), st),
+                  "mtcp_gpu_rto_send_dev")
+
+    def rto_sweep(self, snd: np.ndarray, dtx: np.ndarray, cur_ts: int, cap: int):
+        """mtcp_gpu_rto_sweep over `snd` and `dtx` ((max_id + 1) records each,
+        updated in place); returns (rto, seg_sid, seg_start, seg_stop, total):
+        rto and seg_sid cut to the handled streams, seg_start of cap + 1 and
+        seg_stop of cap zeros, total = (due, handled)."""
+        max_id = len(snd) - 1
+        for a, dt, name in ((snd, ACK_STATE_DTYPE, "snd"), (dtx, DATAGEN_STATE_DTYPE, "dtx")):
+            if a.dtype != dt or not a.flags.c_contiguous or len(a) != max_id + 1 or max_id < 0:
+                raise ValueError(f"{name}: (max_id + 1) contiguous records of its dtype")
+        n = max(cap, 1)
+        rto, seg_sid = np.zeros(n, dtype=RTO_REC_DTYPE), np.zeros(n, dtype=np.uint32)
+        seg_start, seg_stop = np.full(n + 1, 0xFFFFFFFF, dtype=np.uint32), np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        nseg, total = np.zeros(1, dtype=np.uint32), np.zeros(2, dtype=np.uint64)
+        check(lib().mtcp_gpu_rto_sweep(self._h, max_id, snd.ctypes.data, dtx.ctypes.data, cur_ts & 0xFFFFFFFF, cap,
+                                       rto.ctypes.data, seg_sid.ctypes.data, seg_start.ctypes.data,
+                                       seg_stop.ctypes.data, nseg.ctypes.data, total.ctypes.data),
+              "mtcp_gpu_rto_sweep")
+        m = int(nseg[0])
+        return rto[:m], seg_sid[:m], seg_start, seg_stop, total
 
     # -- the payload copy behind the walk (tcp_ring_buffer.c:304-319; mtcp_gpu_rcvcopy.h) --
     @staticmethod
