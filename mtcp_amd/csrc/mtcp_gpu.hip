@@ -35,6 +35,7 @@
 #include "group_kernels.hpp"
 #include "host_call.hpp"
 #include "host_copy.hpp"
+#include "stage_layout.hpp"
 #include "park.hpp"
 #include "rcvwalk_kernels.hpp"
 #include "ackwalk_kernels.hpp"
@@ -1275,8 +1276,6 @@ int mtcp_gpu_steer_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, uint32_t
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// The records go up into stage 0's record buffer; its chunk buffer holds
-// idx[n], start[Q + 2] (adjacent: they come down together) and the workspace.
 int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, uint32_t flags,
                    uint32_t *idx, uint32_t *start) {
     if (!ctx || (flags & ~MTCP_GPU_STEER_DROP_BAD) || n > MTCP_GPU_STEER_MAX_PKTS ||
@@ -1287,22 +1286,17 @@ int mtcp_gpu_steer(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, uint32_t n, ui
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
     const uint32_t Q = steer_queues(ctx);
-    const uint64_t rbytes = (uint64_t)n * record_size(ctx), ibytes = (uint64_t)n * sizeof(uint32_t);
-    const uint64_t sbytes = ((uint64_t)Q + 2) * sizeof(uint32_t);
-    const uint64_t work_off = (ibytes + sbytes + 15) & ~15ull;
-    const uint64_t wbytes = steer_work(Q, n).bytes;
+    const SteerLayout l(n, Q, record_size(ctx), steer_work(Q, n).bytes);
     Stage &s = ctx->stage[0];
-    int rc = stage_reserve(ctx, s, work_off + wbytes, n, dl);
-    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, rbytes, ibytes + sbytes, dl);
+    int rc = stage_reserve(ctx, s, l.dev_bytes, n, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, l.in_bytes, l.out_bytes(), dl);
     if (rc != MTCP_GPU_OK) return rc;
-    uint32_t *d_idx = reinterpret_cast<uint32_t *>(s.d_buf);
-    uint32_t *d_start = d_idx + n;
     Call hc(s, dl, {ctx, dl});
-    hc.up(s.d_out, res, rbytes);
+    hc.up(s.d_out, res, n * record_size(ctx));
     if (hc.ok())
-        hc.note(mtcp_gpu_steer_dev(ctx, s.d_out, n, flags, d_idx, d_start, nullptr, nullptr, s.d_buf + work_off,
-                                   wbytes, s.stream));
-    hc.down2(idx, d_idx, ibytes, start, sbytes);
+        hc.note(mtcp_gpu_steer_dev(ctx, s.d_out, n, flags, l.idx(s), l.start(s), nullptr, nullptr, l.work(s),
+                                   l.work.bytes, s.stream));
+    hc.down2(idx, l.idx(s), l.idx.bytes, start, l.start.bytes);
     return hc.finish();
 }
 
@@ -1371,8 +1365,6 @@ int mtcp_gpu_group_dev(mtcp_gpu_ctx *ctx, const uint32_t *d_sid, uint32_t n, uin
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Stage 0's chunk buffer holds sid[n], then the outputs in one piece (nseg and
-// 12 B of padding, idx[n], seg_sid[n], seg_start[n + 1]), then the workspace.
 // m is known only on the device: a bounded call brings the whole piece down
 // pinned and copies out what the contract names; an unbounded one fetches idx
 // and nseg, waits, and fetches the table's m and m + 1 entries.
@@ -1385,40 +1377,32 @@ int mtcp_gpu_group(mtcp_gpu_ctx *ctx, const uint32_t *sid, uint32_t n, uint32_t 
     if (n == 0) return MTCP_GPU_OK;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const uint64_t ibytes = (uint64_t)n * sizeof(uint32_t);
-    const uint64_t out_off = (ibytes + 15) & ~15ull;               // nseg, padded to 16 B
-    const uint64_t obytes = 16 + 3 * ibytes + sizeof(uint32_t);
-    const uint64_t work_off = (out_off + obytes + 15) & ~15ull;
-    const uint64_t wbytes = mg::group_work(n, max_id).bytes;
+    const GroupLayout l(n, mg::group_work(n, max_id).bytes);
     Stage &s = ctx->stage[0];
-    int rc = stage_reserve(ctx, s, work_off + wbytes, 0, dl);
-    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, ibytes, obytes, dl);
+    int rc = stage_reserve(ctx, s, l.dev_bytes, 0, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, l.in_bytes, l.out_bytes(), dl);
     if (rc != MTCP_GPU_OK) return rc;
-    uint32_t *d_sid = reinterpret_cast<uint32_t *>(s.d_buf);
-    uint32_t *d_nseg = reinterpret_cast<uint32_t *>(s.d_buf + out_off);
-    uint32_t *d_idx = d_nseg + 4, *d_seg_sid = d_idx + n, *d_seg_start = d_seg_sid + n;
     Call hc(s, dl, {ctx, dl});
-    hc.up(d_sid, sid, ibytes);
+    hc.up(l.sid(s), sid, l.sid.bytes);
     if (hc.ok())
-        hc.note(mtcp_gpu_group_dev(ctx, d_sid, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, s.d_buf + work_off,
-                                   wbytes, s.stream));
+        hc.note(mtcp_gpu_group_dev(ctx, l.sid(s), n, max_id, l.idx(s), l.seg_sid(s), l.seg_start(s), l.nseg(s),
+                                   l.work(s), l.work.bytes, s.stream));
     if (hc.bounded()) {
         // one wait: nothing has reached the caller when it gives up
-        const uint32_t *h = reinterpret_cast<const uint32_t *>(hc.down_pinned(d_nseg, obytes));
+        const uint8_t *h = hc.down_pinned(s.d_buf + l.back_off, l.back_bytes());
         if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-        const uint32_t m = std::min(h[0], n);
-        nseg[0] = m;
-        memcpy(idx, h + 4, ibytes);
-        memcpy(seg_sid, h + 4 + n, (size_t)m * sizeof(uint32_t));
-        memcpy(seg_start, h + 4 + 2 * (size_t)n, ((size_t)m + 1) * sizeof(uint32_t));
+        l.copy_out(h, {{nseg, l.nseg}});
+        const uint32_t m = nseg[0] = std::min(nseg[0], n);
+        l.copy_out(h, {{idx, l.idx}, {seg_sid, l.seg_sid, (size_t)m * sizeof(uint32_t)},
+                       {seg_start, l.seg_start, ((size_t)m + 1) * sizeof(uint32_t)}});
         return rc;
     }
-    hc.down(idx, d_idx, ibytes);
-    hc.down(nseg, d_nseg, sizeof(uint32_t));
+    hc.down(idx, l.idx(s), l.idx.bytes);
+    hc.down(nseg, l.nseg(s), l.nseg.bytes);
     if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
     const uint32_t m = std::min(nseg[0], n);
-    hc.down(seg_sid, d_seg_sid, (size_t)m * sizeof(uint32_t));
-    hc.down(seg_start, d_seg_start, ((size_t)m + 1) * sizeof(uint32_t));
+    hc.down(seg_sid, l.seg_sid(s), (size_t)m * sizeof(uint32_t));
+    hc.down(seg_start, l.seg_start(s), ((size_t)m + 1) * sizeof(uint32_t));
     return hc.finish();
 }
 
@@ -1466,12 +1450,9 @@ int mtcp_gpu_rcvwalk_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, const 
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Stage 0's chunk buffer holds the inputs (res, opt, idx, seg_sid[m],
-// seg_start[m + 1], nseg, each padded to 16 B), then in one piece what comes
-// back (state[max_id + 1] at a 64 B boundary, place[n], seg_stop[n]), then the
-// workspace.  A bounded call brings the piece down pinned in one wait and
-// copies out what the contract names: nothing has reached the caller when it
-// gives up.
+// A bounded call brings the back piece (RcvwalkLayout) down pinned in one
+// wait and copies out what the contract names: nothing has reached the caller
+// when it gives up.
 int mtcp_gpu_rcvwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_gpu_tcpopt *opt, uint32_t n,
                      uint32_t max_id, const uint32_t *idx, const uint32_t *seg_sid, const uint32_t *seg_start,
                      const uint32_t *nseg, mtcp_gpu_rcv_state *state, mtcp_gpu_rcv_place *place,
@@ -1485,50 +1466,25 @@ int mtcp_gpu_rcvwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_g
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
     const uint32_t m = std::min(nseg[0], n);
-    const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_result), obytes = opt ? (uint64_t)n * sizeof(mtcp_gpu_tcpopt) : 0;
-    const uint64_t ibytes = (uint64_t)n * sizeof(uint32_t), mbytes = (uint64_t)m * sizeof(uint32_t);
-    const uint64_t sbytes = ((uint64_t)max_id + 1) * sizeof(mtcp_gpu_rcv_state);
-    const uint64_t pbytes = (uint64_t)n * sizeof(mtcp_gpu_rcv_place);
-    const uint64_t res_off = 0, opt_off = res_off + pad16(rbytes), idx_off = opt_off + pad16(obytes);
-    const uint64_t sid_off = idx_off + pad16(ibytes), start_off = sid_off + pad16(mbytes);
-    const uint64_t nseg_off = start_off + pad16(mbytes + 4);
-    const uint64_t state_off = (nseg_off + 16 + 63) & ~63ull, place_off = state_off + sbytes;
-    const uint64_t stop_off = place_off + pbytes, back_bytes = sbytes + pbytes + ibytes;
-    const uint64_t work_off = pad16(stop_off + ibytes), wbytes = mg::rcv_work(n).bytes;
+    const RcvwalkLayout l(n, max_id, m, opt != nullptr, false, mg::rcv_work(n).bytes);
     Stage &s = ctx->stage[0];
-    int rc = stage_reserve(ctx, s, work_off + wbytes, 0, dl);
-    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, state_off + sbytes, back_bytes, dl);
+    int rc = stage_reserve(ctx, s, l.dev_bytes, 0, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, l.in_bytes, l.out_bytes(), dl);
     if (rc != MTCP_GPU_OK) return rc;
-    auto at = [&](uint64_t off) { return s.d_buf + off; };
-    mtcp_gpu_rcv_state *d_state = reinterpret_cast<mtcp_gpu_rcv_state *>(at(state_off));
     Call hc(s, dl, {ctx, dl});
-    hc.up(at(res_off), res, rbytes);
-    if (opt) hc.up(at(opt_off), opt, obytes);
-    hc.up(at(idx_off), idx, ibytes);
-    hc.up(at(sid_off), seg_sid, mbytes);
-    hc.up(at(start_off), seg_start, mbytes + 4);
-    hc.up(at(nseg_off), &m, sizeof(uint32_t));
-    hc.up(d_state, state, sbytes);
+    hc.up(l.res(s), res, l.res.bytes);
+    hc.up(l.opt(s), opt, l.opt.bytes);
+    l.g.up(hc, s, idx, seg_sid, seg_start, &m);
+    hc.up(l.state(s), state, l.state.bytes);
     if (hc.ok())
-        hc.note(mtcp_gpu_rcvwalk_dev(ctx, reinterpret_cast<const mtcp_gpu_result *>(at(res_off)),
-                                     opt ? reinterpret_cast<const mtcp_gpu_tcpopt *>(at(opt_off)) : nullptr, n, max_id,
-                                     reinterpret_cast<const uint32_t *>(at(idx_off)),
-                                     reinterpret_cast<const uint32_t *>(at(sid_off)),
-                                     reinterpret_cast<const uint32_t *>(at(start_off)),
-                                     reinterpret_cast<const uint32_t *>(at(nseg_off)), d_state,
-                                     reinterpret_cast<mtcp_gpu_rcv_place *>(at(place_off)),
-                                     reinterpret_cast<uint32_t *>(at(stop_off)), at(work_off), wbytes, s.stream));
-    if (hc.bounded()) {
-        const uint8_t *h = hc.down_pinned(d_state, back_bytes);
-        if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-        memcpy(state, h, sbytes);
-        memcpy(place, h + sbytes, pbytes);
-        memcpy(seg_stop, h + sbytes + pbytes, mbytes);
-        return rc;
-    }
-    hc.down(state, d_state, sbytes);
-    hc.down(place, at(place_off), pbytes);
-    hc.down(seg_stop, at(stop_off), mbytes);
+        hc.note(mtcp_gpu_rcvwalk_dev(ctx, l.res(s), opt ? l.opt(s) : nullptr, n, max_id, l.g.idx(s), l.g.seg_sid(s),
+                                     l.g.seg_start(s), l.g.nseg(s), l.state(s), l.rec(s), l.stop(s), l.work(s),
+                                     l.work.bytes, s.stream));
+    const uint64_t mbytes = (uint64_t)m * sizeof(uint32_t);
+    if (hc.bounded()) return l.fetch(hc, s, {{state, l.state}, {place, l.rec}, {seg_stop, l.stop, mbytes}});
+    hc.down(state, l.state(s), l.state.bytes);
+    hc.down(place, l.rec(s), l.rec.bytes);
+    hc.down(seg_stop, l.stop(s), mbytes);
     return hc.finish();
 }
 
@@ -1579,10 +1535,6 @@ int mtcp_gpu_ackwalk_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *d_res, const 
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Stage 0's chunk buffer as in mtcp_gpu_rcvwalk: the inputs (res, opt, place,
-// idx, seg_sid[m], seg_start[m + 1], nseg, each padded to 16 B), then in one
-// piece what comes back (snd[max_id + 1] at a 128 B boundary, ack[n],
-// ack_stop[n]), then the workspace.
 int mtcp_gpu_ackwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_gpu_tcpopt *opt,
                      const mtcp_gpu_rcv_place *place, uint32_t n, uint32_t max_id, const uint32_t *idx,
                      const uint32_t *seg_sid, const uint32_t *seg_start, const uint32_t *nseg, uint32_t cur_ts,
@@ -1596,53 +1548,26 @@ int mtcp_gpu_ackwalk(mtcp_gpu_ctx *ctx, const mtcp_gpu_result *res, const mtcp_g
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
     const uint32_t m = std::min(nseg[0], n);
-    const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_result), obytes = opt ? (uint64_t)n * sizeof(mtcp_gpu_tcpopt) : 0;
-    const uint64_t pbytes = (uint64_t)n * sizeof(mtcp_gpu_rcv_place);
-    const uint64_t ibytes = (uint64_t)n * sizeof(uint32_t), mbytes = (uint64_t)m * sizeof(uint32_t);
-    const uint64_t sbytes = ((uint64_t)max_id + 1) * sizeof(mtcp_gpu_ack_state);
-    const uint64_t abytes = (uint64_t)n * sizeof(mtcp_gpu_ack_rec);
-    const uint64_t res_off = 0, opt_off = res_off + pad16(rbytes), place_off = opt_off + pad16(obytes);
-    const uint64_t idx_off = place_off + pbytes, sid_off = idx_off + pad16(ibytes), start_off = sid_off + pad16(mbytes);
-    const uint64_t nseg_off = start_off + pad16(mbytes + 4);
-    const uint64_t snd_off = (nseg_off + 16 + 127) & ~127ull, ack_off = snd_off + sbytes;
-    const uint64_t stop_off = ack_off + abytes, back_bytes = sbytes + abytes + ibytes;
-    const uint64_t work_off = pad16(stop_off + ibytes), wbytes = mg::ack_work(n).bytes;
+    const AckwalkLayout l(n, max_id, m, opt != nullptr, true, mg::ack_work(n).bytes);
     Stage &s = ctx->stage[0];
-    int rc = stage_reserve(ctx, s, work_off + wbytes, 0, dl);
-    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, snd_off + sbytes, back_bytes, dl);
+    int rc = stage_reserve(ctx, s, l.dev_bytes, 0, dl);
+    if (rc == MTCP_GPU_OK && dl.bounded) rc = stage_host(ctx, s, l.in_bytes, l.out_bytes(), dl);
     if (rc != MTCP_GPU_OK) return rc;
-    auto at = [&](uint64_t off) { return s.d_buf + off; };
-    mtcp_gpu_ack_state *d_snd = reinterpret_cast<mtcp_gpu_ack_state *>(at(snd_off));
     Call hc(s, dl, {ctx, dl});
-    hc.up(at(res_off), res, rbytes);
-    if (opt) hc.up(at(opt_off), opt, obytes);
-    hc.up(at(place_off), place, pbytes);
-    hc.up(at(idx_off), idx, ibytes);
-    hc.up(at(sid_off), seg_sid, mbytes);
-    hc.up(at(start_off), seg_start, mbytes + 4);
-    hc.up(at(nseg_off), &m, sizeof(uint32_t));
-    hc.up(d_snd, snd, sbytes);
+    hc.up(l.res(s), res, l.res.bytes);
+    hc.up(l.opt(s), opt, l.opt.bytes);
+    hc.up(l.place(s), place, l.place.bytes);
+    l.g.up(hc, s, idx, seg_sid, seg_start, &m);
+    hc.up(l.state(s), snd, l.state.bytes);
     if (hc.ok())
-        hc.note(mtcp_gpu_ackwalk_dev(ctx, reinterpret_cast<const mtcp_gpu_result *>(at(res_off)),
-                                     opt ? reinterpret_cast<const mtcp_gpu_tcpopt *>(at(opt_off)) : nullptr,
-                                     reinterpret_cast<const mtcp_gpu_rcv_place *>(at(place_off)), n, max_id,
-                                     reinterpret_cast<const uint32_t *>(at(idx_off)),
-                                     reinterpret_cast<const uint32_t *>(at(sid_off)),
-                                     reinterpret_cast<const uint32_t *>(at(start_off)),
-                                     reinterpret_cast<const uint32_t *>(at(nseg_off)), cur_ts, d_snd,
-                                     reinterpret_cast<mtcp_gpu_ack_rec *>(at(ack_off)),
-                                     reinterpret_cast<uint32_t *>(at(stop_off)), at(work_off), wbytes, s.stream));
-    if (hc.bounded()) {
-        const uint8_t *h = hc.down_pinned(d_snd, back_bytes);
-        if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-        memcpy(snd, h, sbytes);
-        memcpy(ack, h + sbytes, abytes);
-        memcpy(ack_stop, h + sbytes + abytes, mbytes);
-        return rc;
-    }
-    hc.down(snd, d_snd, sbytes);
-    hc.down(ack, at(ack_off), abytes);
-    hc.down(ack_stop, at(stop_off), mbytes);
+        hc.note(mtcp_gpu_ackwalk_dev(ctx, l.res(s), opt ? l.opt(s) : nullptr, l.place(s), n, max_id, l.g.idx(s),
+                                     l.g.seg_sid(s), l.g.seg_start(s), l.g.nseg(s), cur_ts, l.state(s), l.rec(s),
+                                     l.stop(s), l.work(s), l.work.bytes, s.stream));
+    const uint64_t mbytes = (uint64_t)m * sizeof(uint32_t);
+    if (hc.bounded()) return l.fetch(hc, s, {{snd, l.state}, {ack, l.rec}, {ack_stop, l.stop, mbytes}});
+    hc.down(snd, l.state(s), l.state.bytes);
+    hc.down(ack, l.rec(s), l.rec.bytes);
+    hc.down(ack_stop, l.stop(s), mbytes);
     return hc.finish();
 }
 
@@ -1965,6 +1890,16 @@ uint64_t grown(uint64_t need, uint64_t have) {
     return cap;
 }
 
+// Stage s for a call laid out by l that brings its results down pinned in
+// either mode, behind first_bytes of its own (a tx call's image).
+int stage_pinned(mtcp_gpu_ctx *ctx, Stage &s, const StageLayout &l, uint64_t first_bytes, uint32_t pkts,
+                 const Deadline &dl) {
+    const int rc = stage_reserve(ctx, s, grown(l.dev_bytes, s.buf_cap), pkts, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    return stage_host(ctx, s, dl.bounded ? grown(l.in_bytes, s.h_in_cap) : 0,
+                      grown(l.out_bytes(first_bytes), s.h_out_cap), dl);
+}
+
 }  // namespace
 
 int mtcp_gpu_tx_build_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *d_seg, uint32_t n,
@@ -2011,10 +1946,9 @@ int mtcp_gpu_tx_build_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *d_seg, uint3
     return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
 }
 
-// Stage 0's chunk buffer holds the frames' image, then the payload, the
-// records, the links and the status bytes; the image is never uploaded (the
-// builder reads no frame byte) and comes down pinned, whole, with the status
-// bytes behind it, from where only the built frames' bytes reach buf.
+// The image is never uploaded (the builder reads no frame byte) and comes
+// down pinned, whole, with the status bytes behind it, from where only the
+// built frames' bytes reach buf.
 int mtcp_gpu_tx_build(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *seg, uint32_t n,
                       const void *payload, uint64_t payload_bytes,
                       const mtcp_gpu_tx_link *links, uint32_t n_links,
@@ -2029,31 +1963,20 @@ int mtcp_gpu_tx_build(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_seg *seg, uint32_t n,
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
     Stage &s = ctx->stage[0];
-    const uint64_t sbytes = (uint64_t)n * sizeof(mtcp_gpu_tx_seg), lbytes = (uint64_t)n_links * sizeof(mtcp_gpu_tx_link);
-    const uint64_t dbytes = (uint64_t)n * sizeof(mtcp_gpu_desc);
-    const uint64_t pay_off = pad16(buf_len), seg_off = pay_off + pad16(payload_bytes), link_off = seg_off + pad16(sbytes);
-    const uint64_t st_off = link_off + pad16(lbytes), total = st_off + pad16(n);
-    // host side: in = payload | records | links | descriptors (bounded calls), out = image | status
-    const uint64_t hin_total = pad16(payload_bytes) + pad16(sbytes) + pad16(lbytes) + dbytes, hout_total = pay_off + n;
-    int rc = stage_reserve(ctx, s, grown(total, s.buf_cap), (uint32_t)grown(n, s.pkt_cap), dl);
-    if (rc == MTCP_GPU_OK)
-        rc = stage_host(ctx, s, dl.bounded ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
+    const TxLayout l(n, n_links, payload_bytes, buf_len);
+    int rc = stage_pinned(ctx, s, l, buf_len, (uint32_t)grown(n, s.pkt_cap), dl);
     if (rc != MTCP_GPU_OK) return rc;
     Call hc(s, dl, {ctx, dl});
-    hc.up(s.d_buf + pay_off, payload, payload_bytes, true);
-    hc.up(s.d_buf + seg_off, seg, sbytes);
-    hc.up(s.d_buf + link_off, links, lbytes);
-    hc.up(s.d_desc, desc, dbytes);
+    hc.up(l.payload(s), payload, payload_bytes, true);
+    hc.up(l.seg(s), seg, l.seg.bytes);
+    hc.up(l.links(s), links, l.links.bytes);
+    hc.up(s.d_desc, desc, (uint64_t)n * sizeof(mtcp_gpu_desc));
     if (hc.ok())
-        hc.note(mtcp_gpu_tx_build_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_seg *>(s.d_buf + seg_off), n,
-                                      s.d_buf + pay_off, payload_bytes,
-                                      reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
-                                      buf_len, s.d_desc, off_shift, max_mss, flags, s.d_buf + st_off, s.stream));
-    const uint8_t *image = hc.down_pinned(s.d_buf, buf_len);
-    const uint8_t *st = hc.down_pinned(s.d_buf + st_off, n);
-    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-    const uint32_t cnt = copy_built(buf, image, buf_len, desc, st, n, off_shift);
-    memcpy(status, st, n);
+        hc.note(mtcp_gpu_tx_build_dev(ctx, l.seg(s), n, l.payload(s), payload_bytes, l.links(s), n_links, l.image(s),
+                                      buf_len, s.d_desc, off_shift, max_mss, flags, l.status(s), s.stream));
+    const uint8_t *image = hc.down_pinned(l.image(s), buf_len);
+    if ((rc = l.fetch(hc, s, {{status, l.status}})) != MTCP_GPU_OK) return rc;
+    const uint32_t cnt = copy_built(buf, image, buf_len, desc, status, n, off_shift);
     if (n_built) *n_built = cnt;
     return MTCP_GPU_OK;
 }
@@ -2215,11 +2138,9 @@ int mtcp_gpu_tx_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *d_burst, ui
                                  d_desc, off_shift, max_mss, flags, d_status, stream);
 }
 
-// Stage 0's chunk buffer holds the frames' image, then the payload, the
-// bursts, the links, the segment records, the descriptors, the status bytes,
-// the results, the totals and the workspace; the image is never uploaded and
-// comes down pinned, whole, with the descriptors, status bytes, results and
-// totals behind it, from where only the built frames' bytes reach buf.
+// The image is never uploaded and comes down pinned, whole, with the
+// descriptors, status bytes, results and totals behind it (TxLayout),
+// from where only the built frames' bytes reach buf.
 int mtcp_gpu_tx_send(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *burst, uint32_t n_burst,
                      const void *payload, uint64_t payload_bytes,
                      const mtcp_gpu_tx_link *links, uint32_t n_links,
@@ -2236,49 +2157,22 @@ int mtcp_gpu_tx_send(mtcp_gpu_ctx *ctx, const mtcp_gpu_tx_burst *burst, uint32_t
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
     Stage &s = ctx->stage[0];
-    const uint64_t bbytes = (uint64_t)n_burst * sizeof(mtcp_gpu_tx_burst);
-    const uint64_t lbytes = (uint64_t)n_links * sizeof(mtcp_gpu_tx_link);
-    const uint64_t sbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_tx_seg);
-    const uint64_t dbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_desc);
-    const uint64_t rbytes = (uint64_t)n_burst * sizeof(mtcp_gpu_tx_burst_result);
-    const uint64_t wbytes = txseg_work(n_burst).bytes;
-    // device: image | payload | bursts | links | records | [descriptors | status | results | totals] | workspace
-    const uint64_t pay_off = pad16(buf_len), burst_off = pay_off + pad16(payload_bytes), link_off = burst_off + pad16(bbytes);
-    const uint64_t seg_off = link_off + pad16(lbytes), desc_off = seg_off + pad16(sbytes);
-    const uint64_t st_off = desc_off + pad16(dbytes), res_off = st_off + pad16(seg_cap), tot_off = res_off + pad16(rbytes);
-    const uint64_t work_off = tot_off + 16, dev_total = work_off + wbytes;
-    const uint64_t back = work_off - desc_off;                   // the bracketed part comes back in one copy
-    // host side: in = payload | bursts | links (bounded calls), out = image | the bracketed part
-    const uint64_t hin_total = pad16(payload_bytes) + pad16(bbytes) + pad16(lbytes), hout_total = pay_off + back;
-    int rc = stage_reserve(ctx, s, grown(dev_total, s.buf_cap), 0, dl);
-    if (rc == MTCP_GPU_OK)
-        rc = stage_host(ctx, s, dl.bounded ? grown(hin_total, s.h_in_cap) : 0, grown(hout_total, s.h_out_cap), dl);
+    const TxLayout l(n_burst, n_links, payload_bytes, buf_len, seg_cap, txseg_work(n_burst).bytes);
+    int rc = stage_pinned(ctx, s, l, buf_len, 0, dl);
     if (rc != MTCP_GPU_OK) return rc;
     Call hc(s, dl, {ctx, dl});
-    hc.up(s.d_buf + pay_off, payload, payload_bytes, true);
-    hc.up(s.d_buf + burst_off, burst, bbytes);
-    hc.up(s.d_buf + link_off, links, lbytes);
+    hc.up(l.payload(s), payload, payload_bytes, true);
+    hc.up(l.burst(s), burst, l.burst.bytes);
+    hc.up(l.links(s), links, l.links.bytes);
     if (hc.ok())
-        hc.note(mtcp_gpu_tx_send_dev(ctx, reinterpret_cast<const mtcp_gpu_tx_burst *>(s.d_buf + burst_off), n_burst,
-                                     s.d_buf + pay_off, payload_bytes,
-                                     reinterpret_cast<const mtcp_gpu_tx_link *>(s.d_buf + link_off), n_links, s.d_buf,
-                                     buf_off, buf_len, off_shift, slot_bytes, max_mss, flags,
-                                     reinterpret_cast<mtcp_gpu_tx_seg *>(s.d_buf + seg_off),
-                                     reinterpret_cast<mtcp_gpu_desc *>(s.d_buf + desc_off), seg_cap,
-                                     reinterpret_cast<mtcp_gpu_tx_burst_result *>(s.d_buf + res_off),
-                                     reinterpret_cast<uint64_t *>(s.d_buf + tot_off), s.d_buf + st_off,
-                                     s.d_buf + work_off, wbytes, s.stream));
-    const uint8_t *image = hc.down_pinned(s.d_buf, buf_len);
-    const uint8_t *hb = hc.down_pinned(s.d_buf + desc_off, back);
-    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-    const mtcp_gpu_desc *hd = reinterpret_cast<const mtcp_gpu_desc *>(hb);
-    const uint8_t *hs = hb + (st_off - desc_off);
-    copy_built(buf, image, buf_len, hd, hs, seg_cap, off_shift);
-    memcpy(desc, hd, dbytes);
-    memcpy(status, hs, seg_cap);
-    if (rbytes) memcpy(res, hb + (res_off - desc_off), rbytes);
-    memcpy(total, hb + (tot_off - desc_off), 16);
-    return MTCP_GPU_OK;
+        hc.note(mtcp_gpu_tx_send_dev(ctx, l.burst(s), n_burst, l.payload(s), payload_bytes, l.links(s), n_links,
+                                     l.image(s), buf_off, buf_len, off_shift, slot_bytes, max_mss, flags, l.seg(s),
+                                     l.desc(s), seg_cap, l.res(s), l.total(s), l.status(s), l.work(s), l.work.bytes,
+                                     s.stream));
+    const uint8_t *image = hc.down_pinned(l.image(s), buf_len);
+    rc = l.fetch(hc, s, {{desc, l.desc}, {status, l.status}, {res, l.res}, {total, l.total}});
+    if (rc == MTCP_GPU_OK) copy_built(buf, image, buf_len, desc, status, seg_cap, off_shift);
+    return rc;
 }
 
 // ---- pure-ACK tx segments from a walked rx batch ----------------
@@ -2406,10 +2300,6 @@ int mtcp_gpu_ack_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcv_place *d_place, 
                                  0, flags, d_status, stream);
 }
 
-// Stage 0's chunk buffer: the inputs (place, idx, seg_sid[m], seg_start[m + 1],
-// nseg, seg_stop[m], ack_stop[m], state and snd at their alignments), then in
-// one piece what comes back (tx[max_id + 1], seg[seg_cap], desc[seg_cap],
-// ares[n], total[2]), then the workspace.
 int mtcp_gpu_ackgen(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcv_place *place, uint32_t n, uint32_t max_id,
                     const uint32_t *idx, const uint32_t *seg_sid, const uint32_t *seg_start, const uint32_t *nseg,
                     const uint32_t *seg_stop, const uint32_t *ack_stop, const mtcp_gpu_rcv_state *state,
@@ -2425,60 +2315,26 @@ int mtcp_gpu_ackgen(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcv_place *place, uint32_t
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
     const uint32_t m = n ? std::min(nseg[0], n) : 0u;
-    const uint64_t ids = n ? (uint64_t)max_id + 1 : 0;
-    const uint64_t pbytes = (uint64_t)n * sizeof(mtcp_gpu_rcv_place), ibytes = (uint64_t)n * sizeof(uint32_t);
-    const uint64_t mbytes = (uint64_t)m * sizeof(uint32_t);
-    const uint64_t stbytes = ids * sizeof(mtcp_gpu_rcv_state), snbytes = ids * sizeof(mtcp_gpu_ack_state);
-    const uint64_t txbytes = ids * sizeof(mtcp_gpu_ackgen_state);
-    const uint64_t sgbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_tx_seg), dbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_desc);
-    const uint64_t abytes = (uint64_t)n * sizeof(mtcp_gpu_ackgen_res);
-    const uint64_t place_off = 0, idx_off = place_off + pbytes, sid_off = idx_off + pad16(ibytes);
-    const uint64_t start_off = sid_off + pad16(mbytes), nseg_off = start_off + pad16(mbytes + 4);
-    const uint64_t stop_off = nseg_off + 16, astop_off = stop_off + pad16(mbytes);
-    const uint64_t snd_off = (astop_off + pad16(mbytes) + 127) & ~127ull, state_off = snd_off + snbytes;
-    const uint64_t tx_off = state_off + stbytes;                              // 32 B aligned: both are multiples of 64
-    const uint64_t seg_off = tx_off + txbytes, desc_off = seg_off + sgbytes, ares_off = desc_off + pad16(dbytes);
-    const uint64_t tot_off = ares_off + abytes, back_bytes = tot_off + 16 - tx_off;
-    const uint64_t work_off = tot_off + 16, wbytes = mg::ackgen_work(n).bytes;
+    const AckgenLayout l(false, n, max_id, m, ack_stop != nullptr, seg_cap, mg::ackgen_work(n).bytes);
     Stage &s = ctx->stage[0];
-    int rc = stage_reserve(ctx, s, grown(work_off + wbytes, s.buf_cap), 0, dl);
-    if (rc == MTCP_GPU_OK)
-        rc = stage_host(ctx, s, dl.bounded ? grown(tx_off + txbytes, s.h_in_cap) : 0, grown(back_bytes, s.h_out_cap), dl);
+    int rc = stage_pinned(ctx, s, l, 0, 0, dl);
     if (rc != MTCP_GPU_OK) return rc;
-    auto at = [&](uint64_t off) { return s.d_buf + off; };
-    auto u32p = [&](uint64_t off) { return reinterpret_cast<const uint32_t *>(at(off)); };
     Call hc(s, dl, {ctx, dl});
     if (n) {
-        hc.up(at(place_off), place, pbytes);
-        hc.up(at(idx_off), idx, ibytes);
-        hc.up(at(sid_off), seg_sid, mbytes);
-        hc.up(at(start_off), seg_start, mbytes + 4);
-        hc.up(at(nseg_off), &m, sizeof(uint32_t));
-        hc.up(at(stop_off), seg_stop, mbytes);
-        if (ack_stop) hc.up(at(astop_off), ack_stop, mbytes);
-        hc.up(at(snd_off), snd, snbytes);
-        hc.up(at(state_off), state, stbytes);
-        hc.up(at(tx_off), tx, txbytes);
+        hc.up(l.in_rec(s), place, l.in_rec.bytes);
+        l.g.up(hc, s, idx, seg_sid, seg_start, &m, seg_stop, ack_stop);
+        hc.up(l.snd(s), snd, l.snd.bytes);
+        hc.up(l.state(s), state, l.state.bytes);
+        hc.up(l.tx(s), tx, l.tx.bytes);
     }
     if (hc.ok())
-        hc.note(mtcp_gpu_ackgen_dev(ctx, reinterpret_cast<const mtcp_gpu_rcv_place *>(at(place_off)), n, max_id,
-                                    u32p(idx_off), u32p(sid_off), u32p(start_off), u32p(nseg_off), u32p(stop_off),
-                                    ack_stop ? u32p(astop_off) : nullptr,
-                                    reinterpret_cast<const mtcp_gpu_rcv_state *>(at(state_off)),
-                                    reinterpret_cast<const mtcp_gpu_ack_state *>(at(snd_off)), cur_ts,
-                                    reinterpret_cast<mtcp_gpu_ackgen_state *>(at(tx_off)), n_links, buf_off, buf_len,
-                                    off_shift, slot_bytes, reinterpret_cast<mtcp_gpu_tx_seg *>(at(seg_off)),
-                                    reinterpret_cast<mtcp_gpu_desc *>(at(desc_off)), seg_cap,
-                                    reinterpret_cast<mtcp_gpu_ackgen_res *>(at(ares_off)),
-                                    reinterpret_cast<uint64_t *>(at(tot_off)), at(work_off), wbytes, s.stream));
-    const uint8_t *h = hc.down_pinned(at(tx_off), back_bytes);
-    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-    if (txbytes) memcpy(tx, h, txbytes);
-    memcpy(seg, h + (seg_off - tx_off), sgbytes);
-    memcpy(desc, h + (desc_off - tx_off), dbytes);
-    if (m) memcpy(ares, h + (ares_off - tx_off), (uint64_t)m * sizeof(mtcp_gpu_ackgen_res));
-    memcpy(total, h + (tot_off - tx_off), 16);
-    return MTCP_GPU_OK;
+        hc.note(mtcp_gpu_ackgen_dev(ctx, l.in_rec(s), n, max_id, l.g.idx(s), l.g.seg_sid(s), l.g.seg_start(s),
+                                    l.g.nseg(s), l.g.seg_stop(s), ack_stop ? l.g.ack_stop(s) : nullptr, l.state(s),
+                                    l.snd(s), cur_ts, l.tx(s), n_links, buf_off, buf_len, off_shift, slot_bytes,
+                                    l.seg(s), l.desc(s), seg_cap, l.res(s), l.total(s), l.work(s), l.work.bytes,
+                                    s.stream));
+    return l.fetch(hc, s, {{tx, l.tx}, {seg, l.seg}, {desc, l.desc},
+                           {ares, l.res, (uint64_t)m * sizeof(mtcp_gpu_ackgen_res)}, {total, l.total}});
 }
 
 // ---- data tx segments from a walked rx batch ---------------------
@@ -2608,10 +2464,6 @@ int mtcp_gpu_data_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_ack_rec *d_ack, con
                                  d_desc, off_shift, max_mss, flags, d_status, stream);
 }
 
-// Stage 0's chunk buffer: the inputs (ack, idx, seg_sid[m], seg_start[m + 1],
-// nseg, seg_stop[m], ack_stop[m] and state at their alignments), then in one
-// piece what comes back (snd, tx and dtx[max_id + 1], seg[seg_cap],
-// desc[seg_cap], dres[n], total[2]), then the workspace.
 int mtcp_gpu_datagen(mtcp_gpu_ctx *ctx, const mtcp_gpu_ack_rec *ack, const uint32_t *ack_stop, uint32_t n,
                      uint32_t max_id, const uint32_t *idx, const uint32_t *seg_sid, const uint32_t *seg_start,
                      const uint32_t *nseg, const uint32_t *seg_stop, const mtcp_gpu_rcv_state *state,
@@ -2628,66 +2480,27 @@ int mtcp_gpu_datagen(mtcp_gpu_ctx *ctx, const mtcp_gpu_ack_rec *ack, const uint3
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
     const uint32_t m = n ? std::min(nseg[0], n) : 0u;
-    const uint64_t ids = n ? (uint64_t)max_id + 1 : 0;
-    const uint64_t abytes = (uint64_t)n * sizeof(mtcp_gpu_ack_rec), ibytes = (uint64_t)n * sizeof(uint32_t);
-    const uint64_t mbytes = (uint64_t)m * sizeof(uint32_t);
-    const uint64_t stbytes = ids * sizeof(mtcp_gpu_rcv_state), snbytes = ids * sizeof(mtcp_gpu_ack_state);
-    const uint64_t txbytes = ids * sizeof(mtcp_gpu_ackgen_state), dtbytes = ids * sizeof(mtcp_gpu_datagen_state);
-    const uint64_t sgbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_tx_seg), dbytes = (uint64_t)seg_cap * sizeof(mtcp_gpu_desc);
-    const uint64_t rbytes = (uint64_t)n * sizeof(mtcp_gpu_datagen_res);
-    const uint64_t ack_off = 0, idx_off = ack_off + abytes, sid_off = idx_off + pad16(ibytes);
-    const uint64_t start_off = sid_off + pad16(mbytes), nseg_off = start_off + pad16(mbytes + 4);
-    const uint64_t stop_off = nseg_off + 16, astop_off = stop_off + pad16(mbytes);
-    const uint64_t state_off = (astop_off + pad16(mbytes) + 127) & ~127ull;
-    const uint64_t snd_off = (state_off + stbytes + 127) & ~127ull;          // what comes back begins here
-    const uint64_t tx_off = snd_off + snbytes, dtx_off = tx_off + txbytes;    // multiples of 128 and of 32
-    const uint64_t seg_off = dtx_off + dtbytes, desc_off = seg_off + sgbytes, res_off = desc_off + pad16(dbytes);
-    const uint64_t tot_off = res_off + rbytes, back_bytes = tot_off + 16 - snd_off;
-    const uint64_t work_off = tot_off + 16, wbytes = datagen_work_total(n);
+    const DatagenLayout l(true, n, max_id, m, ack != nullptr, seg_cap, datagen_work_total(n));
     Stage &s = ctx->stage[0];
-    int rc = stage_reserve(ctx, s, grown(work_off + wbytes, s.buf_cap), 0, dl);
-    if (rc == MTCP_GPU_OK)
-        rc = stage_host(ctx, s, dl.bounded ? grown(seg_off, s.h_in_cap) : 0, grown(back_bytes, s.h_out_cap), dl);
+    int rc = stage_pinned(ctx, s, l, 0, 0, dl);
     if (rc != MTCP_GPU_OK) return rc;
-    auto at = [&](uint64_t off) { return s.d_buf + off; };
-    auto u32p = [&](uint64_t off) { return reinterpret_cast<const uint32_t *>(at(off)); };
     Call hc(s, dl, {ctx, dl});
     if (n) {
-        if (ack) hc.up(at(ack_off), ack, abytes);
-        hc.up(at(idx_off), idx, ibytes);
-        hc.up(at(sid_off), seg_sid, mbytes);
-        hc.up(at(start_off), seg_start, mbytes + 4);
-        hc.up(at(nseg_off), &m, sizeof(uint32_t));
-        hc.up(at(stop_off), seg_stop, mbytes);
-        if (ack_stop) hc.up(at(astop_off), ack_stop, mbytes);
-        hc.up(at(state_off), state, stbytes);
-        hc.up(at(snd_off), snd, snbytes);
-        hc.up(at(tx_off), tx, txbytes);
-        hc.up(at(dtx_off), dtx, dtbytes);
+        if (ack) hc.up(l.in_rec(s), ack, l.in_rec.bytes);
+        l.g.up(hc, s, idx, seg_sid, seg_start, &m, seg_stop, ack_stop);
+        hc.up(l.state(s), state, l.state.bytes);
+        hc.up(l.snd(s), snd, l.snd.bytes);
+        hc.up(l.tx(s), tx, l.tx.bytes);
+        hc.up(l.dtx(s), dtx, l.dtx.bytes);
     }
     if (hc.ok())
-        hc.note(mtcp_gpu_datagen_dev(ctx, ack ? reinterpret_cast<const mtcp_gpu_ack_rec *>(at(ack_off)) : nullptr,
-                                     ack_stop ? u32p(astop_off) : nullptr, n, max_id, u32p(idx_off), u32p(sid_off),
-                                     u32p(start_off), u32p(nseg_off), u32p(stop_off),
-                                     reinterpret_cast<const mtcp_gpu_rcv_state *>(at(state_off)),
-                                     reinterpret_cast<mtcp_gpu_ack_state *>(at(snd_off)),
-                                     reinterpret_cast<mtcp_gpu_ackgen_state *>(at(tx_off)),
-                                     reinterpret_cast<mtcp_gpu_datagen_state *>(at(dtx_off)), cur_ts, payload_bytes,
-                                     n_links, buf_off, buf_len, off_shift, slot_bytes, max_mss,
-                                     reinterpret_cast<mtcp_gpu_tx_seg *>(at(seg_off)),
-                                     reinterpret_cast<mtcp_gpu_desc *>(at(desc_off)), seg_cap,
-                                     reinterpret_cast<mtcp_gpu_datagen_res *>(at(res_off)),
-                                     reinterpret_cast<uint64_t *>(at(tot_off)), at(work_off), wbytes, s.stream));
-    const uint8_t *h = hc.down_pinned(at(snd_off), back_bytes);
-    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-    if (snbytes) memcpy(snd, h, snbytes);
-    if (txbytes) memcpy(tx, h + (tx_off - snd_off), txbytes);
-    if (dtbytes) memcpy(dtx, h + (dtx_off - snd_off), dtbytes);
-    memcpy(seg, h + (seg_off - snd_off), sgbytes);
-    memcpy(desc, h + (desc_off - snd_off), dbytes);
-    if (m) memcpy(dres, h + (res_off - snd_off), (uint64_t)m * sizeof(mtcp_gpu_datagen_res));
-    memcpy(total, h + (tot_off - snd_off), 16);
-    return MTCP_GPU_OK;
+        hc.note(mtcp_gpu_datagen_dev(ctx, ack ? l.in_rec(s) : nullptr, ack_stop ? l.g.ack_stop(s) : nullptr, n, max_id,
+                                     l.g.idx(s), l.g.seg_sid(s), l.g.seg_start(s), l.g.nseg(s), l.g.seg_stop(s),
+                                     l.state(s), l.snd(s), l.tx(s), l.dtx(s), cur_ts, payload_bytes, n_links, buf_off,
+                                     buf_len, off_shift, slot_bytes, max_mss, l.seg(s), l.desc(s), seg_cap, l.res(s),
+                                     l.total(s), l.work(s), l.work.bytes, s.stream));
+    return l.fetch(hc, s, {{snd, l.snd}, {tx, l.tx}, {dtx, l.dtx}, {seg, l.seg}, {desc, l.desc},
+                           {dres, l.res, (uint64_t)m * sizeof(mtcp_gpu_datagen_res)}, {total, l.total}});
 }
 
 // ---- the retransmission-timeout sweep over device send states ----
@@ -2791,9 +2604,6 @@ int mtcp_gpu_rto_send_dev(mtcp_gpu_ctx *ctx, uint32_t max_id, mtcp_gpu_ack_state
                                   d_desc, seg_cap, d_dres, d_dtotal, d_status, d_work, work_bytes, stream);
 }
 
-// Stage 0's chunk buffer: in one piece what goes up and comes back (snd and
-// dtx[max_id + 1]) and what comes back only (rto[cap], seg_sid[cap],
-// seg_start[cap + 1], seg_stop[cap], nseg, total[2]), then the workspace.
 int mtcp_gpu_rto_sweep(mtcp_gpu_ctx *ctx, uint32_t max_id, mtcp_gpu_ack_state *snd, mtcp_gpu_datagen_state *dtx,
                        uint32_t cur_ts, uint32_t cap, mtcp_gpu_rto_rec *rto, uint32_t *seg_sid, uint32_t *seg_start,
                        uint32_t *seg_stop, uint32_t *nseg, uint64_t total[2]) {
@@ -2803,45 +2613,24 @@ int mtcp_gpu_rto_sweep(mtcp_gpu_ctx *ctx, uint32_t max_id, mtcp_gpu_ack_state *s
     if (ctx->abandoned) return MTCP_GPU_EIO;
     DeviceGuard dg(ctx->device);
     const Deadline dl(ctx->wait_us);
-    const uint64_t ids = (uint64_t)max_id + 1;
-    const uint64_t snbytes = ids * sizeof(mtcp_gpu_ack_state), dtbytes = ids * sizeof(mtcp_gpu_datagen_state);
-    const uint64_t rbytes = (uint64_t)cap * sizeof(mtcp_gpu_rto_rec), cbytes = (uint64_t)cap * sizeof(uint32_t);
-    const uint64_t snd_off = 0, dtx_off = snd_off + snbytes, rto_off = dtx_off + dtbytes;   // multiples of 128 and of 16
-    const uint64_t sid_off = rto_off + rbytes, start_off = sid_off + pad16(cbytes);
-    const uint64_t stop_off = start_off + pad16(cbytes + 4), nseg_off = stop_off + pad16(cbytes);
-    const uint64_t tot_off = nseg_off + 16, back_bytes = tot_off + 16;
-    const uint64_t work_off = back_bytes, wbytes = mg::rto_sweep_work(max_id).bytes;
+    const RtoLayout l(max_id, cap, mg::rto_sweep_work(max_id).bytes);
     Stage &s = ctx->stage[0];
-    int rc = stage_reserve(ctx, s, grown(work_off + wbytes, s.buf_cap), 0, dl);
-    if (rc == MTCP_GPU_OK)
-        rc = stage_host(ctx, s, dl.bounded ? grown(rto_off, s.h_in_cap) : 0, grown(back_bytes, s.h_out_cap), dl);
+    int rc = stage_pinned(ctx, s, l, 0, 0, dl);
     if (rc != MTCP_GPU_OK) return rc;
-    auto at = [&](uint64_t off) { return s.d_buf + off; };
-    auto u32p = [&](uint64_t off) { return reinterpret_cast<uint32_t *>(at(off)); };
     Call hc(s, dl, {ctx, dl});
-    hc.up(at(snd_off), snd, snbytes);
-    hc.up(at(dtx_off), dtx, dtbytes);
+    hc.up(l.snd(s), snd, l.snd.bytes);
+    hc.up(l.dtx(s), dtx, l.dtx.bytes);
     if (hc.ok())
-        hc.note(mtcp_gpu_rto_sweep_dev(ctx, max_id, reinterpret_cast<mtcp_gpu_ack_state *>(at(snd_off)),
-                                       reinterpret_cast<mtcp_gpu_datagen_state *>(at(dtx_off)), cur_ts, cap,
-                                       reinterpret_cast<mtcp_gpu_rto_rec *>(at(rto_off)), u32p(sid_off),
-                                       u32p(start_off), u32p(stop_off), u32p(nseg_off),
-                                       reinterpret_cast<uint64_t *>(at(tot_off)), at(work_off), wbytes, s.stream));
-    const uint8_t *h = hc.down_pinned(at(snd_off), back_bytes);
+        hc.note(mtcp_gpu_rto_sweep_dev(ctx, max_id, l.snd(s), l.dtx(s), cur_ts, cap, l.rto(s), l.seg_sid(s),
+                                       l.seg_start(s), l.seg_stop(s), l.nseg(s), l.total(s), l.work(s), l.work.bytes,
+                                       s.stream));
+    const uint8_t *h = hc.down_pinned(s.d_buf + l.back_off, l.back_bytes());
     if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
-    uint32_t handled;
-    memcpy(&handled, h + nseg_off, sizeof(handled));
-    handled = std::min(handled, cap);
-    memcpy(snd, h + snd_off, snbytes);
-    memcpy(dtx, h + dtx_off, dtbytes);
-    if (handled) {
-        memcpy(rto, h + rto_off, (uint64_t)handled * sizeof(mtcp_gpu_rto_rec));
-        memcpy(seg_sid, h + sid_off, (uint64_t)handled * sizeof(uint32_t));
-    }
-    memcpy(seg_start, h + start_off, cbytes + 4);
-    memcpy(seg_stop, h + stop_off, cbytes);
-    memcpy(nseg, h + nseg_off, sizeof(uint32_t));
-    memcpy(total, h + tot_off, 16);
+    l.copy_out(h, {{nseg, l.nseg}});
+    const uint32_t handled = std::min(nseg[0], cap);
+    l.copy_out(h, {{snd, l.snd}, {dtx, l.dtx}, {rto, l.rto, (uint64_t)handled * sizeof(mtcp_gpu_rto_rec)},
+                   {seg_sid, l.seg_sid, (uint64_t)handled * sizeof(uint32_t)}, {seg_start, l.seg_start},
+                   {seg_stop, l.seg_stop}, {total, l.total}});
     return MTCP_GPU_OK;
 }
 
