@@ -36,6 +36,7 @@ EXPORTS = (
     "mtcp_gpu_group_tile", "mtcp_gpu_group_work_bytes", "mtcp_gpu_group_dev", "mtcp_gpu_group",
     "mtcp_gpu_rcvwalk_work_bytes", "mtcp_gpu_rcvwalk_short_len", "mtcp_gpu_rcvwalk_dev", "mtcp_gpu_rcvwalk",
     "mtcp_gpu_rcvcopy_work_bytes", "mtcp_gpu_rcvcopy_dev",
+    "mtcp_gpu_rcvread_work_bytes", "mtcp_gpu_rcvread_tile", "mtcp_gpu_rcvread_dev", "mtcp_gpu_rcvread",
     "mtcp_gpu_ackwalk_work_bytes", "mtcp_gpu_ackwalk_short_len", "mtcp_gpu_ackwalk_dev", "mtcp_gpu_ackwalk",
     "mtcp_gpu_ackgen_work_bytes", "mtcp_gpu_ackgen_lane_len", "mtcp_gpu_ackgen_dev", "mtcp_gpu_ack_send_dev",
     "mtcp_gpu_ackgen",
@@ -170,6 +171,10 @@ def lib() -> ctypes.CDLL:
         "mtcp_gpu_rcvcopy_work_bytes": ([u32, u32], u64),
         "mtcp_gpu_rcvcopy_dev": ([vp, vp, u64, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64,
                                   vp], i32),
+        "mtcp_gpu_rcvread_work_bytes": ([u32, u32], u64),
+        "mtcp_gpu_rcvread_tile": ([], u32),
+        "mtcp_gpu_rcvread_dev": ([vp, vp, u32, u32, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp], i32),
+        "mtcp_gpu_rcvread": ([vp, vp, u32, u32, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp], i32),
         "mtcp_gpu_pktgen_dev": ([vp, u64, vp, u32, u32, u64, u64, vp], i32),
         "mtcp_gpu_rxq_create": ([ctypes.POINTER(vp), vp, u32, u64], i32),
         "mtcp_gpu_rxq_destroy": ([vp], None),

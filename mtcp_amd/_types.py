@@ -199,3 +199,18 @@ assert RCV_BUF_DTYPE.itemsize == 32
 assert [RCV_BUF_DTYPE.fields[f][1] for f in RCV_BUF_DTYPE.names] == [0, 8, 12, 16, 20, 24]
 RCVCOPY_STATS = ("NONE", "FRONT", "ORDERED", "BAD_BUF", "BAD_SRC", "BAD_RANGE")
 RCVCOPY_WAVE_LEN = 64
+
+# include/mtcp_gpu_rcvread.h: struct mtcp_gpu_rcvread_req (one application read:
+# CopyToUser's stream, len and user buffer, api.c:1114-1149) and struct
+# mtcp_gpu_rcvread_res (what the read returned and what the host replays)
+RCVREAD_REQ_DTYPE = np.dtype([("sid", "<u4"), ("len", "<u4"), ("dst_off", "<u8"), ("flags", "<u4"),
+                              ("rsvd", "<u4", (3,))])
+RCVREAD_RES_DTYPE = np.dtype([("sid", "<u4"), ("copylen", "<u4"), ("rcv_wnd", "<u4"), ("verdict", "u1"),
+                              ("flags", "u1"), ("rsvd", "<u2")])
+assert RCVREAD_REQ_DTYPE.itemsize == 32 and RCVREAD_RES_DTYPE.itemsize == 16
+assert [RCVREAD_REQ_DTYPE.fields[f][1] for f in RCVREAD_REQ_DTYPE.names] == [0, 4, 8, 16, 20]
+assert [RCVREAD_RES_DTYPE.fields[f][1] for f in RCVREAD_RES_DTYPE.names] == [0, 4, 8, 12, 13, 14]
+RCVREAD_VERDICTS = ("NONE", "BAD_REQ", "DUP", "BAD_STATE", "DEFER_STATE", "EAGAIN", "PEEKED", "READ")
+RCVREAD_PEEK, RCVREAD_ON_ACKQ = 0x1, 0x2
+RCVREAD_MORE, RCVREAD_WND_ADV, RCVREAD_FRAG_FREED = 0x1, 0x2, 0x4
+RCVREAD_HOST_MAX_BYTES = 32 << 20

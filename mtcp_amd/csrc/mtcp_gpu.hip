@@ -22,6 +22,7 @@
 #include "../../include/mtcp_gpu_ackwalk.h"
 #include "../../include/mtcp_gpu_ackgen.h"
 #include "../../include/mtcp_gpu_datagen.h"
+#include "../../include/mtcp_gpu_rcvread.h"
 #include "../../include/mtcp_gpu_rtosweep.h"
 #include "../../include/mtcp_gpu_rcvcopy.h"
 #include "../../include/mtcp_gpu_steer.h"
@@ -42,6 +43,7 @@
 #include "ackgen_kernels.hpp"
 #include "datagen_kernels.hpp"
 #include "rtosweep_kernels.hpp"
+#include "rcvread_kernels.hpp"    // last: the kernels of the rows before it keep their place in the code object
 #include "rcvcopy_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
@@ -2631,6 +2633,145 @@ int mtcp_gpu_rto_sweep(mtcp_gpu_ctx *ctx, uint32_t max_id, mtcp_gpu_ack_state *s
     l.copy_out(h, {{snd, l.snd}, {dtx, l.dtx}, {rto, l.rto, (uint64_t)handled * sizeof(mtcp_gpu_rto_rec)},
                    {seg_sid, l.seg_sid, (uint64_t)handled * sizeof(uint32_t)}, {seg_start, l.seg_start},
                    {seg_stop, l.seg_stop}, {total, l.total}});
+    return MTCP_GPU_OK;
+}
+
+// ---- the batched application read out of device receive buffers ----
+static_assert(sizeof(mtcp_gpu_rcvread_req) == 32 && offsetof(mtcp_gpu_rcvread_req, len) == 4 &&
+              offsetof(mtcp_gpu_rcvread_req, dst_off) == 8 && offsetof(mtcp_gpu_rcvread_req, flags) == 16 &&
+              offsetof(mtcp_gpu_rcvread_req, rsvd) == 20,
+              "rcvread_step.hpp reads the request as dwords");
+static_assert(sizeof(mtcp_gpu_rcvread_res) == 16 && offsetof(mtcp_gpu_rcvread_res, copylen) == 4 &&
+              offsetof(mtcp_gpu_rcvread_res, rcv_wnd) == 8 && offsetof(mtcp_gpu_rcvread_res, verdict) == 12 &&
+              offsetof(mtcp_gpu_rcvread_res, flags) == 13 && offsetof(mtcp_gpu_rcvread_res, rsvd) == 14,
+              "rcvread_step.hpp writes the record as dwords");
+static_assert(offsetof(mtcp_gpu_rcv_state, rcv_wnd) == 4 && offsetof(mtcp_gpu_rcv_state, head_seq) == 8 &&
+              offsetof(mtcp_gpu_rcv_state, merged_len) == 12 && offsetof(mtcp_gpu_rcv_state, size) == 16 &&
+              offsetof(mtcp_gpu_rcv_state, tcp_state) == 28 && offsetof(mtcp_gpu_rcv_state, nfrag) == 30 &&
+              offsetof(mtcp_gpu_rcv_state, frag) == 32 && offsetof(mtcp_gpu_rcv_buf, size) == 8 &&
+              offsetof(mtcp_gpu_rcv_buf, head_offset) == 12 && offsetof(mtcp_gpu_rcv_buf, last_len) == 20 &&
+              sizeof(mtcp_gpu_ackgen_state) == 32 && offsetof(mtcp_gpu_ackgen_state, need_wnd_adv) == 19 &&
+              sizeof(mtcp_gpu_ack_state) == 128 && offsetof(mtcp_gpu_ack_state, eff_mss) == 78,
+              "read_step's dwords and rcvread_plan_kernel's loads and stores");
+
+namespace {
+
+bool rcvread_geom_ok(uint32_t n, uint32_t max_id) {
+    return n <= MTCP_GPU_GROUP_MAX_PKTS && max_id <= MTCP_GPU_FLOWTAB_MAX_ID;
+}
+
+// what both forms ask of the device-resident arguments
+bool rcvread_mirrors_ok(const mtcp_gpu_ctx *ctx, uint32_t n, uint32_t max_id, const void *d_state, const void *d_rbuf,
+                        const void *d_tx, const void *d_snd, const void *d_arena, uint64_t arena_bytes) {
+    if (!ctx || !rcvread_geom_ok(n, max_id) || (n && (!d_state || !d_rbuf || !d_arena)) || !d_tx != !d_snd) return false;
+    return !(((uintptr_t)d_state & 63) || ((uintptr_t)d_snd & 127) || ((uintptr_t)d_rbuf & 31) ||
+             ((uintptr_t)d_tx & 31) || ((uintptr_t)d_arena & 15) || (arena_bytes & 15));
+}
+
+// The five launches; d_pack: the synchronous form's gather offsets, or nullptr.
+int rcvread_launch(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcvread_req *d_req, uint32_t n, uint32_t max_id,
+                   mtcp_gpu_rcv_state *d_state, mtcp_gpu_rcv_buf *d_rbuf, mtcp_gpu_ackgen_state *d_tx,
+                   const mtcp_gpu_ack_state *d_snd, const void *d_arena, uint64_t arena_bytes, void *d_dst,
+                   uint64_t dst_bytes, uint64_t store_bytes, const uint64_t *d_pack, mtcp_gpu_rcvread_res *d_rres,
+                   uint64_t *d_total, void *d_work, hipStream_t st) {
+    const mg::ReadWork w = mg::read_work(n, max_id);
+    const mg::ReadParams P{n, max_id, arena_bytes, dst_bytes};
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint32_t *claim = reinterpret_cast<uint32_t *>(work + w.claim_off);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(work + w.cnt_off);
+    uint32_t *part = reinterpret_cast<uint32_t *>(work + w.part_off);
+    uint32_t *tot = reinterpret_cast<uint32_t *>(work + w.tot_off);
+    uint4 *plan = reinterpret_cast<uint4 *>(work + w.plan_off);
+    const uint4 *req = reinterpret_cast<const uint4 *>(d_req);
+    const dim3 block(mg::kBlock), grid(w.nwg);
+    hipLaunchKernelGGL(mg::rcvread_clear_kernel, grid, block, 0, st, req, P, claim, d_total);
+    hipLaunchKernelGGL(mg::rcvread_claim_kernel, grid, block, 0, st, req, P, claim);
+    hipLaunchKernelGGL(mg::rcvread_plan_kernel, grid, block, 0, st, req, P, claim, reinterpret_cast<uint4 *>(d_state),
+                       reinterpret_cast<uint32_t *>(d_rbuf), reinterpret_cast<uint8_t *>(d_tx),
+                       reinterpret_cast<const uint8_t *>(d_snd), d_pack, reinterpret_cast<uint4 *>(d_rres), d_total,
+                       cnt, part, plan);
+    hipLaunchKernelGGL(mg::steer_scan_kernel, dim3(1), block, 0, st, part, w.nwg, tot);
+    // a wave per unit up to eight workgroups a CU; the grid walks what is beyond with its stride.  The units of
+    // disjoint ranges: one per request for a ragged end, and the bytes that can be stored
+    const uint64_t units = (uint64_t)n + std::min(store_bytes, arena_bytes) / mg::kReadUnit;
+    const uint64_t wgs = (units + mg::kWavesPerBlock - 1) / mg::kWavesPerBlock;
+    const uint32_t cgrid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)ctx->num_cu * 8);
+    hipLaunchKernelGGL(mg::rcvread_copy_kernel, dim3(cgrid), block, 0, st, cnt, part, tot, w.nwg, plan,
+                       (uint64_t)(uintptr_t)d_arena, (uint64_t)(uintptr_t)d_dst);
+    ctx->last_kernel = "rcvread_copy_kernel";
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+}  // namespace
+
+uint32_t mtcp_gpu_rcvread_tile(void) { return mg::kReadUnit; }
+
+uint64_t mtcp_gpu_rcvread_work_bytes(uint32_t n, uint32_t max_id) {
+    if (!rcvread_geom_ok(n, max_id)) return 0;
+    return mg::read_work(n, max_id).bytes;
+}
+
+int mtcp_gpu_rcvread_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcvread_req *d_req, uint32_t n, uint32_t max_id,
+                         mtcp_gpu_rcv_state *d_state, mtcp_gpu_rcv_buf *d_rbuf, mtcp_gpu_ackgen_state *d_tx,
+                         const mtcp_gpu_ack_state *d_snd, const void *d_arena, uint64_t arena_bytes, void *d_dst,
+                         uint64_t dst_bytes, mtcp_gpu_rcvread_res *d_rres, uint64_t *d_total, void *d_work,
+                         uint64_t work_bytes, void *stream) {
+    if (!rcvread_mirrors_ok(ctx, n, max_id, d_state, d_rbuf, d_tx, d_snd, d_arena, arena_bytes) ||
+        (n && (!d_req || !d_dst || !d_rres || !d_total || !d_work)) || ((uintptr_t)d_req & 15) ||
+        ((uintptr_t)d_dst & 15) || ((uintptr_t)d_rres & 15) || ((uintptr_t)d_total & 7) || ((uintptr_t)d_work & 15) ||
+        (n && work_bytes < mg::read_work(n, max_id).bytes))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    return rcvread_launch(ctx, d_req, n, max_id, d_state, d_rbuf, d_tx, d_snd, d_arena, arena_bytes, d_dst, dst_bytes,
+                          dst_bytes, nullptr, d_rres, d_total, d_work, pick(ctx, stream));
+}
+
+int mtcp_gpu_rcvread(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcvread_req *req, uint32_t n, uint32_t max_id,
+                     mtcp_gpu_rcv_state *d_state, mtcp_gpu_rcv_buf *d_rbuf, mtcp_gpu_ackgen_state *d_tx,
+                     const mtcp_gpu_ack_state *d_snd, const void *d_arena, uint64_t arena_bytes, void *dst,
+                     uint64_t dst_bytes, mtcp_gpu_rcvread_res *rres, uint64_t total[2]) {
+    if (!rcvread_mirrors_ok(ctx, n, max_id, d_state, d_rbuf, d_tx, d_snd, d_arena, arena_bytes) ||
+        (n && (!req || !dst || !rres || !total)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    // the gather: request i's bytes at pack[i] of the stage, len bytes each, 16 B aligned.  The bound is tested
+    // before the table is allocated, and no exception leaves a C entry point
+    uint64_t gather = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if ((gather += pad16(req[i].len)) > MTCP_GPU_RCVREAD_HOST_MAX_BYTES) return MTCP_GPU_EINVAL;
+    std::vector<uint64_t> pack;
+    try {
+        pack.resize(n);
+    } catch (const std::bad_alloc &) {
+        return MTCP_GPU_ENOMEM;
+    }
+    gather = 0;
+    for (uint32_t i = 0; i < n; ++i) pack[i] = gather, gather += pad16(req[i].len);
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const RcvreadLayout l(n, gather, mg::read_work(n, max_id).bytes);
+    Stage &s = ctx->stage[0];
+    int rc = stage_pinned(ctx, s, l, 0, 0, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    Call hc(s, dl, {ctx, dl});
+    hc.up(l.req(s), req, l.req.bytes);
+    hc.up(l.pack(s), pack.data(), l.pack.bytes);
+    if (hc.ok())
+        hc.note(rcvread_launch(ctx, l.req(s), n, max_id, d_state, d_rbuf, d_tx, d_snd, d_arena, arena_bytes,
+                               l.bytes(s), dst_bytes, gather, l.pack(s), l.rres(s), l.total(s), l.work(s), s.stream));
+    const uint8_t *h = hc.down_pinned(s.d_buf + l.back_off, l.back_bytes());
+    if ((rc = hc.finish()) != MTCP_GPU_OK) return rc;
+    l.copy_out(h, {{rres, l.rres}, {total, l.total}});
+    const uint8_t *bytes = h + (l.bytes.off - l.back_off);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t len = rres[i].copylen;
+        // what the device checked, once more before host memory is written
+        if (len && len <= req[i].len && req[i].dst_off <= dst_bytes && len <= dst_bytes - req[i].dst_off)
+            memcpy(static_cast<uint8_t *>(dst) + req[i].dst_off, bytes + pack[i], len);
+    }
     return MTCP_GPU_OK;
 }
 

@@ -5,6 +5,7 @@
 #pragma once
 #include <initializer_list>
 
+#include "../../include/mtcp_gpu_rcvread.h"
 #include "../../include/mtcp_gpu_rtosweep.h"   // and through it the records of every row before it
 #include "host_call.hpp"
 
@@ -176,6 +177,19 @@ struct RtoLayout : StageLayout {
         put(snd, max_id + 1ull, kIn | kBack, 128), put(dtx, max_id + 1ull, kIn | kBack), put(rto, cap, kBack);
         put(seg_sid, cap, kBack), put(seg_start, cap + 1ull, kBack), put(seg_stop, cap, kBack);
         put(nseg, 1, kBack), put(total, 2, kBack);
+        end(wbytes);
+    }
+};
+
+// mtcp_gpu_rcvread: the requests and the gather's offsets go up; the records,
+// the totals and the gathered bytes (gather_bytes of them) come back.
+struct RcvreadLayout : StageLayout {
+    Reg<mtcp_gpu_rcvread_req> req;
+    Reg<uint64_t> pack, total;
+    Reg<mtcp_gpu_rcvread_res> rres;
+    Reg<uint8_t> bytes;
+    RcvreadLayout(uint32_t n, uint64_t gather_bytes, uint64_t wbytes) {
+        put(req, n, kIn), put(pack, n, kIn), put(rres, n, kBack), put(total, 2, kBack), put(bytes, gather_bytes, kBack);
         end(wbytes);
     }
 };

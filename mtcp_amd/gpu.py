@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, DATAGEN_RES_DTYPE, DATAGEN_STATE_DTYPE, RTO_REC_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, DATAGEN_RES_DTYPE, DATAGEN_STATE_DTYPE, RCVREAD_REQ_DTYPE, RCVREAD_RES_DTYPE, RTO_REC_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -672,6 +672,46 @@ class Context:
                                              _dptr(rbuf), _dptr(arena), arena.numel() * arena.element_size(),
                                              _dptr(cstat), _dptr(work), work.numel() * work.element_size(), st),
                   "mtcp_gpu_rcvcopy_dev")
+
+    # -- the application read out of the arena (api.c:1096-1149, tcp_ring_buffer.c:384-421; mtcp_gpu_rcvread.h) --
+    @staticmethod
+    def rcvread_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_rcvread_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_rcvread_work_bytes(n, max_id)
+
+    @staticmethod
+    def rcvread_tile() -> int:
+        return lib().mtcp_gpu_rcvread_tile()
+
+    def rcvread_dev(self, req, n: int, max_id: int, state, rbuf, tx, snd, arena, dst, rres, total, work,
+                    stream=None) -> None:
+        """req: n x 32 B (RCVREAD_REQ_DTYPE); state: (max_id + 1) x 64 B and rbuf:
+        x 32 B, updated; tx (x 32 B, byte 19 updated) and snd (x 128 B): both or
+        neither None; arena: the receive buffers' bytes, read; dst: the
+        destination region, written; rres: n x 16 B (RCVREAD_RES_DTYPE); total:
+        2 x u64 (requests that copied, bytes); work: at least
+        rcvread_work_bytes(n, max_id) bytes."""
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_rcvread_dev(self._h, _dptr(req), n, max_id, _dptr(state), _dptr(rbuf),
+                                             None if tx is None else _dptr(tx), None if snd is None else _dptr(snd),
+                                             _dptr(arena), arena.numel() * arena.element_size(), _dptr(dst),
+                                             dst.numel() * dst.element_size(), _dptr(rres), _dptr(total), _dptr(work),
+                                             work.numel() * work.element_size(), st), "mtcp_gpu_rcvread_dev")
+
+    def rcvread(self, req: np.ndarray, max_id: int, state, rbuf, tx, snd, arena, dst: np.ndarray):
+        """mtcp_gpu_rcvread: `req` in host memory, the mirrors and the arena GPU
+        tensors as for rcvread_dev; the bytes read land in the host array
+        `dst` (uint8, in place); returns (rres, total)."""
+        req = np.ascontiguousarray(req, dtype=RCVREAD_REQ_DTYPE)
+        if dst.dtype != np.uint8 or not dst.flags.c_contiguous:
+            raise ValueError("dst: a contiguous uint8 array")
+        n = len(req)
+        rres, total = np.zeros(max(n, 1), dtype=RCVREAD_RES_DTYPE), np.zeros(2, dtype=np.uint64)
+        check(lib().mtcp_gpu_rcvread(self._h, req.ctypes.data, n, max_id, _dptr(state), _dptr(rbuf),
+                                     None if tx is None else _dptr(tx), None if snd is None else _dptr(snd),
+                                     _dptr(arena), arena.numel() * arena.element_size(), dst.ctypes.data, dst.nbytes,
+                                     rres.ctypes.data, total.ctypes.data), "mtcp_gpu_rcvread")
+        return rres[:n], total
 
     # -- tx frames from segment records (tcp_out.c:135-354; mtcp_gpu_txbuild.h) --
     def tx_build_dev(self, seg, n: int, payload, links, buf, desc, off_shift: int, status,
