@@ -7,7 +7,7 @@ ARCH     ?= gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-result
 LIB      := mtcp_amd/lib/libmtcp_gpu.so
 SRCS     := mtcp_amd/csrc/mtcp_gpu.hip mtcp_amd/csrc/pktgen.hip mtcp_amd/csrc/rxq.hip
-DEPS     := $(SRCS) mtcp_amd/csrc/dispatch.hpp mtcp_amd/csrc/rx_kernels.hpp mtcp_amd/csrc/rx_wave.hpp mtcp_amd/csrc/rx_span.hpp mtcp_amd/csrc/host_call.hpp mtcp_amd/csrc/stage_layout.hpp mtcp_amd/csrc/host_copy.hpp mtcp_amd/csrc/park.hpp mtcp_amd/csrc/wait.hpp mtcp_amd/csrc/ctx_internal.hpp mtcp_amd/csrc/flow_kernels.hpp mtcp_amd/csrc/flowtab_kernels.hpp mtcp_amd/csrc/group_kernels.hpp mtcp_amd/csrc/rcvwalk_kernels.hpp mtcp_amd/csrc/rcvcopy_kernels.hpp mtcp_amd/csrc/rcvread_kernels.hpp mtcp_amd/csrc/rcvread_step.hpp mtcp_amd/csrc/ackwalk_kernels.hpp mtcp_amd/csrc/ackgen_kernels.hpp mtcp_amd/csrc/ackgen_step.hpp mtcp_amd/csrc/datagen_kernels.hpp mtcp_amd/csrc/datagen_step.hpp mtcp_amd/csrc/rtosweep_kernels.hpp mtcp_amd/csrc/rto_step.hpp mtcp_amd/csrc/ack_step.hpp mtcp_amd/csrc/tcpopt_kernels.hpp mtcp_amd/csrc/steer_kernels.hpp mtcp_amd/csrc/txbuild_kernels.hpp mtcp_amd/csrc/txseg_kernels.hpp include/mtcp_gpu.h include/mtcp_gpu_pktgen.h include/mtcp_gpu_rxq.h include/mtcp_gpu_tcpopt.h include/mtcp_gpu_steer.h include/mtcp_gpu_txbuild.h include/mtcp_gpu_txseg.h include/mtcp_gpu_flowtab.h include/mtcp_gpu_group.h include/mtcp_gpu_rcvwalk.h include/mtcp_gpu_rcvcopy.h include/mtcp_gpu_ackwalk.h include/mtcp_gpu_ackgen.h include/mtcp_gpu_datagen.h include/mtcp_gpu_rcvread.h include/mtcp_gpu_rtosweep.h
+DEPS     := $(SRCS) mtcp_amd/csrc/dispatch.hpp mtcp_amd/csrc/rx_kernels.hpp mtcp_amd/csrc/rx_wave.hpp mtcp_amd/csrc/rx_span.hpp mtcp_amd/csrc/host_call.hpp mtcp_amd/csrc/stage_layout.hpp mtcp_amd/csrc/host_copy.hpp mtcp_amd/csrc/park.hpp mtcp_amd/csrc/wait.hpp mtcp_amd/csrc/ctx_internal.hpp mtcp_amd/csrc/flow_kernels.hpp mtcp_amd/csrc/flowtab_kernels.hpp mtcp_amd/csrc/group_kernels.hpp mtcp_amd/csrc/rcvwalk_kernels.hpp mtcp_amd/csrc/rcvcopy_kernels.hpp mtcp_amd/csrc/rcvread_kernels.hpp mtcp_amd/csrc/rcvread_step.hpp mtcp_amd/csrc/sndwrite_kernels.hpp mtcp_amd/csrc/sndwrite_step.hpp mtcp_amd/csrc/ackwalk_kernels.hpp mtcp_amd/csrc/ackgen_kernels.hpp mtcp_amd/csrc/ackgen_step.hpp mtcp_amd/csrc/datagen_kernels.hpp mtcp_amd/csrc/datagen_step.hpp mtcp_amd/csrc/rtosweep_kernels.hpp mtcp_amd/csrc/rto_step.hpp mtcp_amd/csrc/ack_step.hpp mtcp_amd/csrc/tcpopt_kernels.hpp mtcp_amd/csrc/steer_kernels.hpp mtcp_amd/csrc/txbuild_kernels.hpp mtcp_amd/csrc/txseg_kernels.hpp include/mtcp_gpu.h include/mtcp_gpu_pktgen.h include/mtcp_gpu_rxq.h include/mtcp_gpu_tcpopt.h include/mtcp_gpu_steer.h include/mtcp_gpu_txbuild.h include/mtcp_gpu_txseg.h include/mtcp_gpu_flowtab.h include/mtcp_gpu_group.h include/mtcp_gpu_rcvwalk.h include/mtcp_gpu_rcvcopy.h include/mtcp_gpu_ackwalk.h include/mtcp_gpu_ackgen.h include/mtcp_gpu_datagen.h include/mtcp_gpu_rcvread.h include/mtcp_gpu_rtosweep.h include/mtcp_gpu_sndwrite.h
 
 .PHONY: all lib oracle ref golden examples clean tools
 
@@ -29,7 +29,7 @@ golden:
 	$(MAKE) -C oracle golden
 
 clean:
-	rm -f $(LIB) tests/c/libmtcp_gpu_testing.so tests/c/rxloop tests/c/admit_test tests/c/park_test tests/c/asan_host tools/libstream_ceiling.so tools/libtcpopt_pattern.so tools/libsteer_pattern.so tools/libtxbuild_pattern.so tools/libtxseg_pattern.so tools/libflowtab_pattern.so tools/libgroup_pattern.so tools/librcvwalk_pattern.so tools/librcvcopy_pattern.so tools/libackwalk_pattern.so tools/libackgen_pattern.so tools/libdatagen_pattern.so tools/librtosweep_pattern.so tools/librcvread_pattern.so
+	rm -f $(LIB) tests/c/libmtcp_gpu_testing.so tests/c/rxloop tests/c/admit_test tests/c/park_test tests/c/asan_host tools/libstream_ceiling.so tools/libtcpopt_pattern.so tools/libsteer_pattern.so tools/libtxbuild_pattern.so tools/libtxseg_pattern.so tools/libflowtab_pattern.so tools/libgroup_pattern.so tools/librcvwalk_pattern.so tools/librcvcopy_pattern.so tools/libackwalk_pattern.so tools/libackgen_pattern.so tools/libdatagen_pattern.so tools/librtosweep_pattern.so tools/librcvread_pattern.so tools/libsndwrite_pattern.so
 	$(MAKE) -C oracle clean
 
 # the probe tools instantiate rx_kernel's profiling / timing-probe variants
@@ -161,6 +161,11 @@ tools/libdatagen_pattern.so: tools/datagen_pattern.hip mtcp_amd/csrc/datagen_ker
 # tools/rcvread_bench.py's yardstick: the read's copy units on the copy kernel's
 # grid, no plan, no search, no shift (not the product)
 tools/librcvread_pattern.so: tools/rcvread_pattern.hip mtcp_amd/csrc/rcvread_kernels.hpp mtcp_amd/csrc/rcvread_step.hpp mtcp_amd/csrc/rcvcopy_kernels.hpp mtcp_amd/csrc/steer_kernels.hpp mtcp_amd/csrc/flow_kernels.hpp mtcp_amd/csrc/rx_kernels.hpp include/mtcp_gpu_rcvread.h include/mtcp_gpu_rcvcopy.h include/mtcp_gpu_rcvwalk.h include/mtcp_gpu.h
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
+
+# tools/sndwrite_bench.py's yardstick: the write's copy units on the copy kernel's
+# grid, no plan, no search, no shift, no move (not the product)
+tools/libsndwrite_pattern.so: tools/sndwrite_pattern.hip mtcp_amd/csrc/sndwrite_kernels.hpp mtcp_amd/csrc/sndwrite_step.hpp mtcp_amd/csrc/rcvread_kernels.hpp mtcp_amd/csrc/rcvread_step.hpp mtcp_amd/csrc/rcvcopy_kernels.hpp mtcp_amd/csrc/steer_kernels.hpp mtcp_amd/csrc/flow_kernels.hpp mtcp_amd/csrc/rx_kernels.hpp include/mtcp_gpu_sndwrite.h include/mtcp_gpu_datagen.h include/mtcp_gpu_ackwalk.h include/mtcp_gpu.h
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 
 # tools/rtosweep_bench.py's yardsticks: the sweep's loads and stores on the same

@@ -44,6 +44,8 @@ EXPORTS = (
     "mtcp_gpu_datagen",
     "mtcp_gpu_rto_sweep_work_bytes", "mtcp_gpu_rto_sweep_tile", "mtcp_gpu_rto_sweep_dev", "mtcp_gpu_rto_sweep",
     "mtcp_gpu_rto_send_dev",
+    "mtcp_gpu_sndwrite_work_bytes", "mtcp_gpu_sndwrite_tile", "mtcp_gpu_sndwrite_dev", "mtcp_gpu_sndwrite",
+    "mtcp_gpu_write_send_dev",
     "mtcp_gpu_rxq_pending", "mtcp_gpu_rxq_flush", "mtcp_gpu_rxq_flush_async", "mtcp_gpu_rxq_wait", "mtcp_gpu_rxq_wait_for", "mtcp_gpu_rxq_get", "mtcp_gpu_rxq_get16", "mtcp_gpu_rxq_frame", "mtcp_gpu_rxq_reset",
 )
 
@@ -175,6 +177,13 @@ def lib() -> ctypes.CDLL:
         "mtcp_gpu_rcvread_tile": ([], u32),
         "mtcp_gpu_rcvread_dev": ([vp, vp, u32, u32, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp], i32),
         "mtcp_gpu_rcvread": ([vp, vp, u32, u32, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp], i32),
+        "mtcp_gpu_sndwrite_work_bytes": ([u32, u32], u64),
+        "mtcp_gpu_sndwrite_tile": ([], u32),
+        "mtcp_gpu_sndwrite_dev": ([vp, vp, u32, u32, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, vp], i32),
+        "mtcp_gpu_sndwrite": ([vp, vp, u32, u32, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp], i32),
+        "mtcp_gpu_write_send_dev": ([vp, vp, u32, u32, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp,
+                                     vp, u32, vp, u32, vp, u64, u64, u32, u32, ctypes.c_uint16, u32, vp, vp, u32, vp,
+                                     vp, vp, vp, u64, vp], i32),
         "mtcp_gpu_pktgen_dev": ([vp, u64, vp, u32, u32, u64, u64, vp], i32),
         "mtcp_gpu_rxq_create": ([ctypes.POINTER(vp), vp, u32, u64], i32),
         "mtcp_gpu_rxq_destroy": ([vp], None),

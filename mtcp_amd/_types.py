@@ -214,3 +214,18 @@ RCVREAD_VERDICTS = ("NONE", "BAD_REQ", "DUP", "BAD_STATE", "DEFER_STATE", "EAGAI
 RCVREAD_PEEK, RCVREAD_ON_ACKQ = 0x1, 0x2
 RCVREAD_MORE, RCVREAD_WND_ADV, RCVREAD_FRAG_FREED = 0x1, 0x2, 0x4
 RCVREAD_HOST_MAX_BYTES = 32 << 20
+
+# include/mtcp_gpu_sndwrite.h: struct mtcp_gpu_sndwrite_req (one application
+# write: CopyFromUser's stream, len and user buffer, api.c:1416-1456) and struct
+# mtcp_gpu_sndwrite_res (what the write returned and what the host replays)
+SNDWRITE_REQ_DTYPE = np.dtype([("sid", "<u4"), ("len", "<u4"), ("src_off", "<u8"), ("flags", "<u4"),
+                               ("rsvd", "<u4", (3,))])
+SNDWRITE_RES_DTYPE = np.dtype([("sid", "<u4"), ("written", "<u4"), ("snd_wnd", "<u4"), ("verdict", "u1"),
+                               ("flags", "u1"), ("rsvd", "<u2")])
+assert SNDWRITE_REQ_DTYPE.itemsize == 32 and SNDWRITE_RES_DTYPE.itemsize == 16
+assert [SNDWRITE_REQ_DTYPE.fields[f][1] for f in SNDWRITE_REQ_DTYPE.names] == [0, 4, 8, 16, 20]
+assert [SNDWRITE_RES_DTYPE.fields[f][1] for f in SNDWRITE_RES_DTYPE.names] == [0, 4, 8, 12, 13, 14]
+SNDWRITE_VERDICTS = ("NONE", "BAD_REQ", "DUP", "BAD_STATE", "DEFER_STATE", "ZERO", "EAGAIN", "NO_SNDBUF", "FULL",
+                     "WRITTEN")
+SNDWRITE_ROOM, SNDWRITE_SEND_LIST_ADD, SNDWRITE_COMPACTED = 0x1, 0x2, 0x4
+SNDWRITE_HOST_MAX_BYTES = 32 << 20

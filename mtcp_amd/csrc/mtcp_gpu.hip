@@ -24,6 +24,7 @@
 #include "../../include/mtcp_gpu_datagen.h"
 #include "../../include/mtcp_gpu_rcvread.h"
 #include "../../include/mtcp_gpu_rtosweep.h"
+#include "../../include/mtcp_gpu_sndwrite.h"
 #include "../../include/mtcp_gpu_rcvcopy.h"
 #include "../../include/mtcp_gpu_steer.h"
 #include "../../include/mtcp_gpu_tcpopt.h"
@@ -43,7 +44,8 @@
 #include "ackgen_kernels.hpp"
 #include "datagen_kernels.hpp"
 #include "rtosweep_kernels.hpp"
-#include "rcvread_kernels.hpp"    // last: the kernels of the rows before it keep their place in the code object
+#include "rcvread_kernels.hpp"
+#include "sndwrite_kernels.hpp"   // last: the kernels of the rows before it keep their place in the code object
 #include "rcvcopy_kernels.hpp"
 #include "rx_kernels.hpp"
 #include "rx_span.hpp"
@@ -2773,6 +2775,189 @@ int mtcp_gpu_rcvread(mtcp_gpu_ctx *ctx, const mtcp_gpu_rcvread_req *req, uint32_
             memcpy(static_cast<uint8_t *>(dst) + req[i].dst_off, bytes + pack[i], len);
     }
     return MTCP_GPU_OK;
+}
+
+// ---- the batched application write into device send buffers ----
+static_assert(sizeof(mtcp_gpu_sndwrite_req) == 32 && offsetof(mtcp_gpu_sndwrite_req, len) == 4 &&
+              offsetof(mtcp_gpu_sndwrite_req, src_off) == 8 && offsetof(mtcp_gpu_sndwrite_req, flags) == 16 &&
+              offsetof(mtcp_gpu_sndwrite_req, rsvd) == 20,
+              "sndwrite_step.hpp reads the request as dwords; the claim kernels read its sid");
+static_assert(sizeof(mtcp_gpu_sndwrite_res) == 16 && offsetof(mtcp_gpu_sndwrite_res, written) == 4 &&
+              offsetof(mtcp_gpu_sndwrite_res, snd_wnd) == 8 && offsetof(mtcp_gpu_sndwrite_res, verdict) == 12 &&
+              offsetof(mtcp_gpu_sndwrite_res, flags) == 13 && offsetof(mtcp_gpu_sndwrite_res, rsvd) == 14,
+              "sndwrite_step.hpp writes the record as dwords");
+static_assert(sizeof(mtcp_gpu_ack_state) == 128 && offsetof(mtcp_gpu_ack_state, snd_wnd) == 8 &&
+              offsetof(mtcp_gpu_ack_state, sb_head_seq) == 64 && offsetof(mtcp_gpu_ack_state, sb_len) == 68 &&
+              offsetof(mtcp_gpu_ack_state, sb_size) == 72 && offsetof(mtcp_gpu_ack_state, mss) == 76 &&
+              offsetof(mtcp_gpu_ack_state, tcp_state) == 80 && offsetof(mtcp_gpu_ack_state, nrtx) == 84 &&
+              offsetof(mtcp_gpu_ack_state, has_sndbuf) == 86 && sizeof(mtcp_gpu_datagen_state) == 16 &&
+              offsetof(mtcp_gpu_datagen_state, sb_base_seq) == 8 && offsetof(mtcp_gpu_datagen_state, on_send_list) == 12,
+              "write_step's dwords and sndwrite_plan_kernel's loads and stores");
+
+namespace {
+
+bool sndwrite_geom_ok(uint32_t n, uint32_t max_id) {
+    return n <= MTCP_GPU_GROUP_MAX_PKTS && max_id <= MTCP_GPU_FLOWTAB_MAX_ID;
+}
+
+// what both forms ask of the device-resident arguments
+bool sndwrite_mirrors_ok(const mtcp_gpu_ctx *ctx, uint32_t n, uint32_t max_id, const void *d_snd, const void *d_dtx,
+                         const void *d_payload, uint64_t payload_bytes) {
+    if (!ctx || !sndwrite_geom_ok(n, max_id) || (n && (!d_snd || !d_dtx || !d_payload))) return false;
+    return !(((uintptr_t)d_snd & 127) || ((uintptr_t)d_dtx & 15) || ((uintptr_t)d_payload & 15) || (payload_bytes & 15));
+}
+
+bool sndwrite_dev_args_ok(const mtcp_gpu_ctx *ctx, const void *d_wreq, uint32_t n, uint32_t max_id, const void *d_snd,
+                          const void *d_dtx, const void *d_src, uint64_t src_bytes, const void *d_payload,
+                          uint64_t payload_bytes, const void *d_wres, const void *d_seg_sid, const void *d_seg_start,
+                          const void *d_seg_stop, const void *d_nseg, const void *d_total, const void *d_work,
+                          uint64_t work_bytes) {
+    if (!sndwrite_mirrors_ok(ctx, n, max_id, d_snd, d_dtx, d_payload, payload_bytes)) return false;
+    if (n && (!d_wreq || !d_src || !d_wres || !d_seg_sid || !d_seg_start || !d_seg_stop || !d_nseg || !d_total ||
+              !d_work))
+        return false;
+    if (((uintptr_t)d_wreq & 15) || ((uintptr_t)d_src & 15) || (src_bytes & 15) || ((uintptr_t)d_wres & 15) ||
+        ((uintptr_t)d_seg_sid & 3) || ((uintptr_t)d_seg_start & 3) || ((uintptr_t)d_seg_stop & 3) ||
+        ((uintptr_t)d_nseg & 3) || ((uintptr_t)d_total & 7) || ((uintptr_t)d_work & 15))
+        return false;
+    return !n || work_bytes >= mg::read_work(n, max_id).bytes;
+}
+
+// The six launches; d_pack: the synchronous form's pack offsets, or nullptr.  d_src: the base the copy reads
+// from, load_bytes of it; src_bytes: what BAD_REQ tests src_off + len against.
+int sndwrite_launch(mtcp_gpu_ctx *ctx, const mtcp_gpu_sndwrite_req *d_wreq, uint32_t n, uint32_t max_id,
+                    mtcp_gpu_ack_state *d_snd, mtcp_gpu_datagen_state *d_dtx, const void *d_src, uint64_t src_bytes,
+                    uint64_t load_bytes, const uint64_t *d_pack, void *d_payload, uint64_t payload_bytes,
+                    mtcp_gpu_sndwrite_res *d_wres, uint32_t *d_seg_sid, uint32_t *d_seg_start, uint32_t *d_seg_stop,
+                    uint32_t *d_nseg, uint64_t *d_total, void *d_work, hipStream_t st) {
+    const mg::ReadWork w = mg::read_work(n, max_id);                // the same claim words, prefixes and plan rows
+    const mg::ReadParams C{n, max_id, 0, 0};
+    const mg::WriteParams P{n, max_id, src_bytes, payload_bytes};
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint32_t *claim = reinterpret_cast<uint32_t *>(work + w.claim_off);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(work + w.cnt_off);
+    uint32_t *part = reinterpret_cast<uint32_t *>(work + w.part_off);
+    uint32_t *tot = reinterpret_cast<uint32_t *>(work + w.tot_off);
+    uint4 *plan = reinterpret_cast<uint4 *>(work + w.plan_off);
+    const uint4 *req = reinterpret_cast<const uint4 *>(d_wreq);
+    const dim3 block(mg::kBlock), grid(w.nwg);
+    hipLaunchKernelGGL(mg::rcvread_clear_kernel, grid, block, 0, st, req, C, claim, d_total);
+    hipLaunchKernelGGL(mg::rcvread_claim_kernel, grid, block, 0, st, req, C, claim);
+    hipLaunchKernelGGL(mg::sndwrite_plan_kernel, grid, block, 0, st, req, P, claim, reinterpret_cast<uint32_t *>(d_snd),
+                       reinterpret_cast<uint32_t *>(d_dtx), d_pack, reinterpret_cast<uint4 *>(d_wres), d_seg_sid,
+                       d_seg_start, d_seg_stop, d_nseg, d_total, cnt, part, plan);
+    hipLaunchKernelGGL(mg::steer_scan_kernel, dim3(1), block, 0, st, part, w.nwg, tot);
+    const uint32_t mgrid = (uint32_t)(((uint64_t)n + mg::kWavesPerBlock - 1) / mg::kWavesPerBlock);
+    hipLaunchKernelGGL(mg::sndwrite_move_kernel, dim3(mgrid), block, 0, st, plan, n, (uint64_t)(uintptr_t)d_payload);
+    // a wave per unit up to eight workgroups a CU; the grid walks what is beyond with its stride.  The units of
+    // disjoint chunks: one per request for a ragged end, and the bytes that can be loaded and stored
+    const uint64_t units = (uint64_t)n + std::min(load_bytes, payload_bytes) / mg::kWriteUnit;
+    const uint64_t wgs = (units + mg::kWavesPerBlock - 1) / mg::kWavesPerBlock;
+    const uint32_t cgrid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)ctx->num_cu * 8);
+    hipLaunchKernelGGL(mg::sndwrite_copy_kernel, dim3(cgrid), block, 0, st, cnt, part, tot, w.nwg, plan,
+                       (uint64_t)(uintptr_t)d_src, (uint64_t)(uintptr_t)d_payload);
+    ctx->last_kernel = "sndwrite_copy_kernel";
+    return HIP_OK(hipGetLastError()) ? MTCP_GPU_OK : MTCP_GPU_EIO;
+}
+
+}  // namespace
+
+uint32_t mtcp_gpu_sndwrite_tile(void) { return mg::kWriteUnit; }
+
+uint64_t mtcp_gpu_sndwrite_work_bytes(uint32_t n, uint32_t max_id) {
+    if (!sndwrite_geom_ok(n, max_id)) return 0;
+    return mg::read_work(n, max_id).bytes;
+}
+
+int mtcp_gpu_sndwrite_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_sndwrite_req *d_wreq, uint32_t n, uint32_t max_id,
+                          mtcp_gpu_ack_state *d_snd, mtcp_gpu_datagen_state *d_dtx, const void *d_src,
+                          uint64_t src_bytes, void *d_payload, uint64_t payload_bytes, mtcp_gpu_sndwrite_res *d_wres,
+                          uint32_t *d_seg_sid, uint32_t *d_seg_start, uint32_t *d_seg_stop, uint32_t *d_nseg,
+                          uint64_t *d_total, void *d_work, uint64_t work_bytes, void *stream) {
+    if (!sndwrite_dev_args_ok(ctx, d_wreq, n, max_id, d_snd, d_dtx, d_src, src_bytes, d_payload, payload_bytes, d_wres,
+                              d_seg_sid, d_seg_start, d_seg_stop, d_nseg, d_total, d_work, work_bytes))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    DeviceGuard dg(ctx->device);
+    return sndwrite_launch(ctx, d_wreq, n, max_id, d_snd, d_dtx, d_src, src_bytes, src_bytes, nullptr, d_payload,
+                           payload_bytes, d_wres, d_seg_sid, d_seg_start, d_seg_stop, d_nseg, d_total, d_work,
+                           pick(ctx, stream));
+}
+
+int mtcp_gpu_write_send_dev(mtcp_gpu_ctx *ctx, const mtcp_gpu_sndwrite_req *d_wreq, uint32_t n, uint32_t max_id,
+                            mtcp_gpu_ack_state *d_snd, mtcp_gpu_datagen_state *d_dtx, const void *d_src,
+                            uint64_t src_bytes, void *d_payload, uint64_t payload_bytes, mtcp_gpu_sndwrite_res *d_wres,
+                            uint32_t *d_seg_sid, uint32_t *d_seg_start, uint32_t *d_seg_stop, uint32_t *d_nseg,
+                            uint64_t *d_wtotal, void *d_wwork, uint64_t wwork_bytes, const uint32_t *d_idx,
+                            const mtcp_gpu_rcv_state *d_state, mtcp_gpu_ackgen_state *d_tx, uint32_t cur_ts,
+                            const mtcp_gpu_tx_link *d_links, uint32_t n_links, void *d_buf, uint64_t buf_off,
+                            uint64_t buf_len, uint32_t off_shift, uint32_t slot_bytes, uint16_t max_mss,
+                            uint32_t flags, mtcp_gpu_tx_seg *d_seg, mtcp_gpu_desc *d_desc, uint32_t seg_cap,
+                            mtcp_gpu_datagen_res *d_dres, uint64_t *d_total, uint8_t *d_status, void *d_work,
+                            uint64_t work_bytes, void *stream) {
+    // both calls' checks before either launches
+    if (!sndwrite_dev_args_ok(ctx, d_wreq, n, max_id, d_snd, d_dtx, d_src, src_bytes, d_payload, payload_bytes, d_wres,
+                              d_seg_sid, d_seg_start, d_seg_stop, d_nseg, d_wtotal, d_wwork, wwork_bytes) ||
+        !datagen_dev_args_ok(ctx, nullptr, nullptr, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop,
+                             d_state, d_snd, d_tx, d_dtx, n_links, buf_off, off_shift, slot_bytes, d_seg, d_desc,
+                             seg_cap, d_dres, d_total, d_work, work_bytes) ||
+        !txbuild_args_ok(ctx, seg_cap, d_seg, d_payload, payload_bytes, d_links, n_links, d_buf, buf_len, d_desc,
+                         off_shift, flags, d_status) ||
+        ((uintptr_t)d_links & 3))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    const int rc = mtcp_gpu_sndwrite_dev(ctx, d_wreq, n, max_id, d_snd, d_dtx, d_src, src_bytes, d_payload,
+                                         payload_bytes, d_wres, d_seg_sid, d_seg_start, d_seg_stop, d_nseg, d_wtotal,
+                                         d_wwork, wwork_bytes, stream);
+    if (rc != MTCP_GPU_OK) return rc;
+    return mtcp_gpu_data_send_dev(ctx, nullptr, nullptr, n, max_id, d_idx, d_seg_sid, d_seg_start, d_nseg, d_seg_stop,
+                                  d_state, d_snd, d_tx, d_dtx, cur_ts, d_payload, payload_bytes, d_links, n_links,
+                                  d_buf, buf_off, buf_len, off_shift, slot_bytes, max_mss, flags, d_seg, d_desc,
+                                  seg_cap, d_dres, d_total, d_status, d_work, work_bytes, stream);
+}
+
+int mtcp_gpu_sndwrite(mtcp_gpu_ctx *ctx, const mtcp_gpu_sndwrite_req *wreq, uint32_t n, uint32_t max_id,
+                      mtcp_gpu_ack_state *d_snd, mtcp_gpu_datagen_state *d_dtx, const void *src, uint64_t src_bytes,
+                      void *d_payload, uint64_t payload_bytes, mtcp_gpu_sndwrite_res *wres, uint32_t *seg_sid,
+                      uint32_t *seg_start, uint32_t *seg_stop, uint32_t *nseg, uint64_t total[2]) {
+    if (!sndwrite_mirrors_ok(ctx, n, max_id, d_snd, d_dtx, d_payload, payload_bytes) ||
+        (n && (!wreq || !src || !wres || !seg_sid || !seg_start || !seg_stop || !nseg || !total)))
+        return MTCP_GPU_EINVAL;
+    if (ctx->abandoned) return MTCP_GPU_EIO;
+    if (n == 0) return MTCP_GPU_OK;
+    // the packing: request i's bytes at pack[i] of the stage, len bytes each, 16 B aligned.  The bound is tested
+    // before the table is allocated, and no exception leaves a C entry point
+    uint64_t packed = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if ((packed += pad16(wreq[i].len)) > MTCP_GPU_SNDWRITE_HOST_MAX_BYTES) return MTCP_GPU_EINVAL;
+    std::vector<uint64_t> pack;
+    try {
+        pack.resize(n);
+    } catch (const std::bad_alloc &) {
+        return MTCP_GPU_ENOMEM;
+    }
+    packed = 0;
+    for (uint32_t i = 0; i < n; ++i) pack[i] = packed, packed += pad16(wreq[i].len);
+    DeviceGuard dg(ctx->device);
+    const Deadline dl(ctx->wait_us);
+    const SndwriteLayout l(n, packed, mg::read_work(n, max_id).bytes);
+    Stage &s = ctx->stage[0];
+    int rc = stage_pinned(ctx, s, l, 0, 0, dl);
+    if (rc != MTCP_GPU_OK) return rc;
+    Call hc(s, dl, {ctx, dl});
+    hc.up(l.req(s), wreq, l.req.bytes);
+    hc.up(l.pack(s), pack.data(), l.pack.bytes);
+    // the bytes of the requests whose range lies inside src: what the device tests too, before host memory is read
+    for (uint32_t i = 0; i < n; ++i)
+        if (wreq[i].len && wreq[i].src_off <= src_bytes && wreq[i].len <= src_bytes - wreq[i].src_off)
+            hc.up(l.bytes(s) + pack[i], static_cast<const uint8_t *>(src) + wreq[i].src_off, wreq[i].len, true);
+    if (hc.ok())
+        hc.note(sndwrite_launch(ctx, l.req(s), n, max_id, d_snd, d_dtx, l.bytes(s), src_bytes, packed, l.pack(s),
+                                d_payload, payload_bytes, l.wres(s), l.seg_sid(s), l.seg_start(s), l.seg_stop(s),
+                                l.nseg(s), l.total(s), l.work(s), s.stream));
+    return l.fetch(hc, s, {{wres, l.wres}, {seg_sid, l.seg_sid}, {seg_start, l.seg_start}, {seg_stop, l.seg_stop},
+                           {nseg, l.nseg}, {total, l.total}});
 }
 
 // ---- RSS-friendly address pool -----------------------------

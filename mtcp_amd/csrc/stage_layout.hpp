@@ -7,6 +7,7 @@
 
 #include "../../include/mtcp_gpu_rcvread.h"
 #include "../../include/mtcp_gpu_rtosweep.h"   // and through it the records of every row before it
+#include "../../include/mtcp_gpu_sndwrite.h"
 #include "host_call.hpp"
 
 namespace mtcp_host {
@@ -190,6 +191,23 @@ struct RcvreadLayout : StageLayout {
     Reg<uint8_t> bytes;
     RcvreadLayout(uint32_t n, uint64_t gather_bytes, uint64_t wbytes) {
         put(req, n, kIn), put(pack, n, kIn), put(rres, n, kBack), put(total, 2, kBack), put(bytes, gather_bytes, kBack);
+        end(wbytes);
+    }
+};
+
+// mtcp_gpu_sndwrite: the requests, the pack offsets and the packed bytes
+// (pack_bytes of them, a slot per request) go up; the records, the table and
+// the totals come back.
+struct SndwriteLayout : StageLayout {
+    Reg<mtcp_gpu_sndwrite_req> req;
+    Reg<uint64_t> pack, total;
+    Reg<uint8_t> bytes;
+    Reg<mtcp_gpu_sndwrite_res> wres;
+    Reg<uint32_t> seg_sid, seg_start, seg_stop, nseg;
+    SndwriteLayout(uint32_t n, uint64_t pack_bytes, uint64_t wbytes) {
+        put(req, n, kIn), put(pack, n, kIn), put(bytes, pack_bytes, kIn | kStreamed);
+        put(wres, n, kBack), put(seg_sid, n, kBack), put(seg_start, n + 1ull, kBack), put(seg_stop, n, kBack);
+        put(nseg, 1, kBack), put(total, 2, kBack);
         end(wbytes);
     }
 };

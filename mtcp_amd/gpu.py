@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import check, lib
 from ._types import (ADDR_ENTRY_DTYPE, DESC_DTYPE, FLOW_ENTRY_DTYPE, FLOWTAB_COUNTERS_DTYPE, MAX_PORT, MIN_PORT, RESULT16_DTYPE, RESULT_DTYPE,
-                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, DATAGEN_RES_DTYPE, DATAGEN_STATE_DTYPE, RCVREAD_REQ_DTYPE, RCVREAD_RES_DTYPE, RTO_REC_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
+                     ACKGEN_RES_DTYPE, ACKGEN_STATE_DTYPE, DATAGEN_RES_DTYPE, DATAGEN_STATE_DTYPE, RCVREAD_REQ_DTYPE, RCVREAD_RES_DTYPE, SNDWRITE_REQ_DTYPE, SNDWRITE_RES_DTYPE, RTO_REC_DTYPE, ACK_REC_DTYPE, ACK_STATE_DTYPE, RCV_PLACE_DTYPE, RCV_STATE_DTYPE, TCPOPT_DTYPE, TX_BURST_DTYPE, TX_BURST_RESULT_DTYPE, TX_LINK_DTYPE, TX_SEG_DTYPE)
 
 F_RSS = 0x1
 F_RSS_ENDIAN = 0x2
@@ -712,6 +712,80 @@ class Context:
                                      _dptr(arena), arena.numel() * arena.element_size(), dst.ctypes.data, dst.nbytes,
                                      rres.ctypes.data, total.ctypes.data), "mtcp_gpu_rcvread")
         return rres[:n], total
+
+    # -- the application write into the send buffers (api.c:1416-1567, tcp_send_buffer.c:116-146; mtcp_gpu_sndwrite.h) --
+    @staticmethod
+    def sndwrite_work_bytes(n: int, max_id: int) -> int:
+        """mtcp_gpu_sndwrite_work_bytes (host only, needs no GPU)."""
+        return lib().mtcp_gpu_sndwrite_work_bytes(n, max_id)
+
+    @staticmethod
+    def sndwrite_tile() -> int:
+        return lib().mtcp_gpu_sndwrite_tile()
+
+    def sndwrite_dev(self, wreq, n: int, max_id: int, snd, dtx, src, payload, wres, seg_sid, seg_start, seg_stop,
+                     nseg, total, work, src_bytes: int | None = None, payload_bytes: int | None = None,
+                     stream=None) -> None:
+        """wreq: n x 32 B (SNDWRITE_REQ_DTYPE); snd: (max_id + 1) x 128 B and dtx:
+        x 16 B, updated; src: the source region, read (a tensor, or an int: the
+        device-accessible address of registered host memory, with src_bytes);
+        payload: the arena the send buffers live in, written; wres: n x 16 B
+        (SNDWRITE_RES_DTYPE); seg_sid, seg_stop: n x u32; seg_start: (n + 1) x
+        u32; nseg: 1 x u32; total: 2 x u64 (requests written, bytes); work: at
+        least sndwrite_work_bytes(n, max_id) bytes."""
+        sptr = src if isinstance(src, int) else _dptr(src)
+        if src_bytes is None:
+            src_bytes = src.numel() * src.element_size()
+        if payload_bytes is None:
+            payload_bytes = payload.numel() * payload.element_size()
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_sndwrite_dev(self._h, _dptr(wreq), n, max_id, _dptr(snd), _dptr(dtx), sptr, src_bytes,
+                                              _dptr(payload), payload_bytes, _dptr(wres), _dptr(seg_sid),
+                                              _dptr(seg_start), _dptr(seg_stop), _dptr(nseg), _dptr(total),
+                                              _dptr(work), work.numel() * work.element_size(), st),
+                  "mtcp_gpu_sndwrite_dev")
+
+    def sndwrite(self, wreq: np.ndarray, max_id: int, snd, dtx, src: np.ndarray, payload):
+        """mtcp_gpu_sndwrite: `wreq` and the source bytes `src` (uint8) in host
+        memory, the mirrors and the arena GPU tensors as for sndwrite_dev;
+        returns (wres, seg_sid, seg_start, seg_stop, nseg, total)."""
+        wreq = np.ascontiguousarray(wreq, dtype=SNDWRITE_REQ_DTYPE)
+        if src.dtype != np.uint8 or not src.flags.c_contiguous:
+            raise ValueError("src: a contiguous uint8 array")
+        n = len(wreq)
+        k = max(n, 1)
+        wres, total = np.zeros(k, dtype=SNDWRITE_RES_DTYPE), np.zeros(2, dtype=np.uint64)
+        seg_sid, seg_start = np.zeros(k, dtype=np.uint32), np.full(k + 1, 0xFFFFFFFF, dtype=np.uint32)
+        seg_stop, nseg = np.full(k, 0xFFFFFFFF, dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+        check(lib().mtcp_gpu_sndwrite(self._h, wreq.ctypes.data, n, max_id, _dptr(snd), _dptr(dtx), src.ctypes.data,
+                                      src.nbytes, _dptr(payload), payload.numel() * payload.element_size(),
+                                      wres.ctypes.data, seg_sid.ctypes.data, seg_start.ctypes.data,
+                                      seg_stop.ctypes.data, nseg.ctypes.data, total.ctypes.data), "mtcp_gpu_sndwrite")
+        return wres[:n], seg_sid[:n], seg_start[:n + 1], seg_stop[:n], nseg, total
+
+    def write_send_dev(self, wreq, n: int, max_id: int, snd, dtx, src, payload, wres, seg_sid, seg_start, seg_stop,
+                       nseg, wtotal, wwork, idx, state, tx, cur_ts: int, links, buf, buf_off: int, off_shift: int,
+                       slot_bytes: int, seg, desc, seg_cap: int, dres, total, status, work, max_mss: int = 0,
+                       flags: int = 0, buf_len: int | None = None, stream=None) -> None:
+        """sndwrite_dev, then data_send_dev over the table the write made (ack and
+        ack_stop None, n bursts), on one stream.  idx: n x u32, any values;
+        wtotal, wwork: the write's totals and workspace; total, work: the data
+        send's (at least datagen_work_bytes(n, max_id) bytes)."""
+        room = buf.numel() * buf.element_size()
+        if buf_len is not None and not 0 <= buf_len <= room:
+            raise ValueError("buf_len: at most the bytes of buf")
+        with self._ordered(stream) as st:
+            check(lib().mtcp_gpu_write_send_dev(self._h, _dptr(wreq), n, max_id, _dptr(snd), _dptr(dtx), _dptr(src),
+                                                src.numel() * src.element_size(), _dptr(payload),
+                                                payload.numel() * payload.element_size(), _dptr(wres), _dptr(seg_sid),
+                                                _dptr(seg_start), _dptr(seg_stop), _dptr(nseg), _dptr(wtotal),
+                                                _dptr(wwork), wwork.numel() * wwork.element_size(), _dptr(idx),
+                                                _dptr(state), _dptr(tx), cur_ts & 0xFFFFFFFF, _dptr(links),
+                                                links.numel() * links.element_size() // 12, _dptr(buf), buf_off,
+                                                room if buf_len is None else buf_len, off_shift, slot_bytes, max_mss,
+                                                flags, _dptr(seg), _dptr(desc), seg_cap, _dptr(dres), _dptr(total),
+                                                _dptr(status), _dptr(work), work.numel() * work.element_size(), st),
+                  "mtcp_gpu_write_send_dev")
 
     # -- tx frames from segment records (tcp_out.c:135-354; mtcp_gpu_txbuild.h) --
     def tx_build_dev(self, seg, n: int, payload, links, buf, desc, off_shift: int, status,
